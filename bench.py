@@ -13,7 +13,14 @@ and the two reduction buffers are all-reduced over RCCL; total work is fixed, so
     context (sgp_ctx_create_multi, RCCL inside libsgp) -- the path the R drop-in takes;
   * N larger than the visible devices, or < 1, is an error: never a silent one-GPU run.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line (with the
+roofline of the dominant kernel, whose HIP events are read inside the timed steps).  --full adds
+what takes runs of its own: the per-phase pass and the per-kernel rooflines with the measured
+store ceiling, and (headline workload only) the CPU baseline.  --dump-outputs DIR writes what
+the last timed step returned (objective.npy, gradient.npy; knot_gradient.npy with --knots) as
+float64 arrays; the inputs are seeded, so equal arguments give equal inputs.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -272,6 +279,20 @@ def plan_run(gpus, devices, env, visible):
     return "library", list(range(gpus))
 
 
+def dump_outputs(out_dir, obj, grad):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as float64
+    DIR/objective.npy (1), DIR/gradient.npy (P) and, with --knots, DIR/knot_gradient.npy (m*d)."""
+    knot = None
+    if isinstance(grad, tuple):
+        grad, knot = grad
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "objective.npy"), np.array([obj], dtype=np.float64))
+    np.save(os.path.join(out_dir, "gradient.npy"), np.asarray(grad, dtype=np.float64).reshape(-1))
+    if knot is not None:
+        np.save(os.path.join(out_dir, "knot_gradient.npy"),
+                np.asarray(knot, dtype=np.float64).reshape(-1))
+
+
 def _visible_gpus():
     import torch
     return torch.cuda.device_count()
@@ -292,7 +313,14 @@ def main():
     ap.add_argument("--m", type=int, default=None)
     ap.add_argument("--d", type=int, default=None,
                     help="C3's input dimension (default 8): times the d > 8 kernels")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the per-phase pass, the per-kernel "
+                         "rooflines with the measured store ceiling and, for the headline "
+                         "workload, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-full", default=None, metavar="OUT_JSON",
                     help="run only SURVEY 8(d)'s full CPU plan (several minutes, no GPU) and "
                          "write it to OUT_JSON")
@@ -407,8 +435,9 @@ def main():
     # gradient passes read the products the row-quadratic passes stored, no GEMM of their own)
     con_key = {"vi": "contract_knm", "fitc": "rowquad_q", "laplace": "rowquad_q"}[args.mode]
     # Inside the timed region HIP events bracket only that kernel's phase, on its launch
-    # stream (read back once, after the region); the per-phase breakdown comes from a short
-    # untimed pass afterwards, so the other phases' event records stay out of the timed steps.
+    # stream (read back once, after the region); with --full the per-phase breakdown comes from
+    # a short untimed pass afterwards, so the other phases' event records stay out of the timed
+    # steps.
     ctx.timing_filter(con_key)
     ctx.enable_timing(True)
     # the steps' theta trajectory is synthetic input: built before the timed region like the
@@ -418,7 +447,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    obj = None
+    obj = grad = None
     for th in thetas:
         obj, grad = runner.eval(th, P["U"], P["delta"])
     torch.cuda.synchronize(dev)
@@ -428,12 +457,16 @@ def main():
     evals = max(ctx.timing_evals(), 1)
     con_avg = {name: ms / evals for name, ms in ctx.timings()}
     ctx.timing_filter(None)
-    ctx.enable_timing(True)
-    for k in range(min(args.steps, 3)):
-        runner.eval(theta_at(args.warmup + args.steps + k), P["U"], P["delta"])
-    torch.cuda.synchronize(dev)
-    pevals = max(ctx.timing_evals(), 1)
-    phase_avg = {name: ms / pevals for name, ms in ctx.timings()}
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, obj, grad)   # every rank holds the reduced results
+    phase_avg = None
+    if args.full:
+        ctx.enable_timing(True)
+        for k in range(min(args.steps, 3)):
+            runner.eval(theta_at(args.warmup + args.steps + k), P["U"], P["delta"])
+        torch.cuda.synchronize(dev)
+        pevals = max(ctx.timing_evals(), 1)
+        phase_avg = {name: ms / pevals for name, ms in ctx.timings()}
     ctx.enable_timing(False)
     elapsed = t1 - t0
     if distributed:
@@ -487,18 +520,20 @@ def main():
                          "traffic": traffic if args.mode == "vi" else None,
                          "kernel": con_key + (" (k_contract<8>)" if d <= 8 else " (k_contract<32>)"),
                          "flops_per_launch": flops},
-            "kernel_rooflines": kernel_rooflines(args.mode, phase_avg, n_loc, m,
-                                                 store_ceiling(n_loc, m, dev_index)),
-            "phases_ms": {k: round(v, 4) for k, v in phase_avg.items()},
-            "phases_note": "HIP-event phase times from 3 evaluations after the timed steps "
-                           "(inside the timed steps only the roofline kernel's phase is timed)",
             "objective": obj,
         }
+        if args.full:
+            out["kernel_rooflines"] = kernel_rooflines(args.mode, phase_avg, n_loc, m,
+                                                       store_ceiling(n_loc, m, dev_index))
+            out["phases_ms"] = {k: round(v, 4) for k, v in phase_avg.items()}
+            out["phases_note"] = ("HIP-event phase times from 3 evaluations after the timed steps "
+                                  "(inside the timed steps only the roofline kernel's phase is "
+                                  "timed)")
         if args.mode == "laplace":
             out["nr_iters_per_eval"] = timed_iters
         if distributed:
             out["collectives"] = "rccl" if not rehearse else "gloo (rehearsal)"
-        if (world == 1 and not args.no_cpu_baseline and args.mode == "vi"
+        if (args.full and world == 1 and not args.no_cpu_baseline and args.mode == "vi"
                 and args.config == "C3" and n == 1_000_000):
             full = None
             fp = os.path.join(ROOT, "profiles", "r3_cpu_baseline_full.json")
@@ -566,23 +601,27 @@ def bench_library_shards(args, devices):
     for dv in sorted(set(devices)):
         torch.cuda.synchronize(dv)
     t0 = time.perf_counter()
-    obj = None
+    obj = grad = None
     for k in range(args.steps):
-        obj, _ = run(args.warmup + k, thetas[k])
+        obj, grad = run(args.warmup + k, thetas[k])
     for dv in sorted(set(devices)):
         torch.cuda.synchronize(dv)
     elapsed = time.perf_counter() - t0
     evals = max(ctx.timing_evals(), 1)
     t_con = dict(ctx.timings()).get(con_key, float("nan")) / evals * 1e-3
-    # per-phase times of shard 0 from a short untimed pass (as the one-GPU line)
     ctx.timing_filter(None)
-    ctx.enable_timing(True)
-    for k in range(min(args.steps, 3)):
-        run(args.warmup + args.steps + k)
-    for dv in sorted(set(devices)):
-        torch.cuda.synchronize(dv)
-    pevals = max(ctx.timing_evals(), 1)
-    phase_avg = {name: ms / pevals for name, ms in ctx.timings()}
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, obj, grad)
+    phase_avg = None
+    if args.full:
+        # per-phase times of shard 0 from a short untimed pass (as the one-GPU line)
+        ctx.enable_timing(True)
+        for k in range(min(args.steps, 3)):
+            run(args.warmup + args.steps + k)
+        for dv in sorted(set(devices)):
+            torch.cuda.synchronize(dv)
+        pevals = max(ctx.timing_evals(), 1)
+        phase_avg = {name: ms / pevals for name, ms in ctx.timings()}
     ctx.enable_timing(False)
     n0 = shard_rows(n, nshards, 0)[1]
     flops = 2.0 * n0 * m * m
@@ -617,16 +656,17 @@ def bench_library_shards(args, devices):
                         "kernel": con_key + " of shard 0"
                                   + (" (k_contract<8>)" if d <= 8 else " (k_contract<32>)"),
                         "flops_per_launch": flops},
-           "kernel_rooflines": kernel_rooflines(args.mode, phase_avg, n0, m,
-                                                store_ceiling(n0, m, devices[0])),
-           "phases_ms": {k: round(v, 4) for k, v in phase_avg.items()},
-           "phases_note": "shard 0's HIP-event phase times from 3 evaluations after the timed "
-                          "steps",
            "objective": obj,
            "collectives": "rccl (in-library, ncclCommInitAll over the distinct devices)",
            "note": "in-library multi-device context (sgp_ctx_create_multi): one process, one "
                    "host worker per distinct device; shards on one device run one after another "
                    "on it"}
+    if args.full:
+        out["kernel_rooflines"] = kernel_rooflines(args.mode, phase_avg, n0, m,
+                                                   store_ceiling(n0, m, devices[0]))
+        out["phases_ms"] = {k: round(v, 4) for k, v in phase_avg.items()}
+        out["phases_note"] = ("shard 0's HIP-event phase times from 3 evaluations after the "
+                              "timed steps")
     if args.mode == "laplace":
         out["nr_iters_per_eval"] = nr_iters[args.warmup:args.warmup + args.steps]
     print(json.dumps(out), flush=True)

@@ -3,6 +3,7 @@
 #   usage (inside gpurun): bash tools/gpu_check.sh TAG [extra bench args]
 set -o pipefail
 T=$1; shift
+set -- --full "$@"   # the bench line with its per-phase and per-kernel figures
 mkdir -p gpurun_out/$T
 export TMPDIR=/tmp
 timeout -k 10 600 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > gpurun_out/$T/pytest.log 2>&1 || { echo "pytest failed"; tail -30 gpurun_out/$T/pytest.log; exit 1; }

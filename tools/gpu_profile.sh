@@ -12,7 +12,7 @@ step() { echo "== $*"; }
 step pytest
 timeout -k 10 600 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $D/pytest.log 2>&1 || { tail -30 $D/pytest.log; exit 1; }
 step bench
-timeout -k 10 400 python3 bench.py > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
 step kernel-trace
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/k -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $D/k.json 2> $D/k.err || { tail -20 $D/k.err; exit 1; }
 step pmc-fetch
@@ -20,11 +20,11 @@ timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D/pf -o r
 step pmc-write
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/pw -o run -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline > $D/pw.json 2> $D/pw.err || { tail -20 $D/pw.err; exit 1; }
 step modes
-timeout -k 10 300 python3 bench.py --mode fitc --steps 3 --warmup 1 --no-cpu-baseline > $D/fitc.json 2> $D/fitc.err || exit 1
-timeout -k 10 300 python3 bench.py --mode laplace --steps 5 --warmup 2 --no-cpu-baseline > $D/laplace.json 2> $D/laplace.err || exit 1
+timeout -k 10 300 python3 bench.py --full --mode fitc --steps 3 --warmup 1 --no-cpu-baseline > $D/fitc.json 2> $D/fitc.err || exit 1
+timeout -k 10 300 python3 bench.py --full --mode laplace --steps 5 --warmup 2 --no-cpu-baseline > $D/laplace.json 2> $D/laplace.err || exit 1
 step shards
 for nn in 125000 250000 500000; do
-  timeout -k 10 200 python3 bench.py --n $nn --steps 10 --warmup 3 --no-cpu-baseline > $D/rows$nn.json 2> $D/rows$nn.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --n $nn --steps 10 --warmup 3 --no-cpu-baseline > $D/rows$nn.json 2> $D/rows$nn.err || exit 1
 done
 tail -1 $D/pytest.log
 echo ok

@@ -6,7 +6,7 @@
 #   steps:
 #     suite[:PATTERN]   pytest -m gpu (PATTERN: a -k expression), log in $D/suite.log
 #     tests:FILES       pytest -m gpu on the comma-separated test files only
-#     bench             the default bench line (bench.py, cpu_baseline included) -> $D/bench.json
+#     bench             the default bench line (bench.py --full, cpu_baseline included) -> $D/bench.json
 #     prof              rocprofv3 --kernel-trace --stats of the bench command -> $D/k/
 #     modes             the secondary lines: C2, the n = 125 000 shard, FITC, C5, knots, the
 #                       in-library 8-shard composition -> $D/run_*.json
@@ -40,29 +40,29 @@ for step in "$@"; do
         $files > "$D/tests.log" 2>&1 || { tail -60 "$D/tests.log"; exit 1; }
       tail -1 "$D/tests.log" ;;
     bench)
-      timeout -k 10 500 python3 bench.py > "$D/bench.json" 2> "$D/bench.err" || { tail -20 "$D/bench.err"; exit 1; }
+      timeout -k 10 500 python3 bench.py --full > "$D/bench.json" 2> "$D/bench.err" || { tail -20 "$D/bench.err"; exit 1; }
       last_json "$D/bench.json" bench ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/k" -o run -- \
-        python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > "$D/k.json" 2> "$D/k.err" || { tail -20 "$D/k.err"; exit 1; }
+        python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > "$D/k.json" 2> "$D/k.err" || { tail -20 "$D/k.err"; exit 1; }
       last_json "$D/k.json" prof ;;
     modes)
       for a in "--config C2 --steps 300 --warmup 20" "--n 125000 --steps 40 --warmup 4" \
                "--mode fitc --steps 6 --warmup 2" "--config C5 --mode laplace --steps 10 --warmup 2" \
                "--knots --steps 6 --warmup 2" "--devices 0,0,0,0,0,0,0,0 --steps 6 --warmup 2"; do
         f="$D/run_$(echo $a | tr -c 'a-zA-Z0-9' '_').json"
-        timeout -k 10 300 python3 bench.py --no-cpu-baseline $a > "$f" 2> "$D/run.err" || { tail -20 "$D/run.err"; exit 1; }
+        timeout -k 10 300 python3 bench.py --full --no-cpu-baseline $a > "$f" 2> "$D/run.err" || { tail -20 "$D/run.err"; exit 1; }
         last_json "$f" "$a"
       done ;;
     c2x4)
       for r in 1 2 3 4; do
-        timeout -k 10 200 python3 bench.py --no-cpu-baseline --config C2 --steps 300 --warmup 20 \
+        timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --config C2 --steps 300 --warmup 20 \
           > "$D/c2_$r.json" 2> "$D/run.err" || { tail -20 "$D/run.err"; exit 1; }
         last_json "$D/c2_$r.json" "c2 $r"
       done ;;
     c2trace)
       timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/c2k" -o run -- \
-        python3 bench.py --no-cpu-baseline --config C2 --steps 60 --warmup 5 > "$D/c2k.json" 2> "$D/c2k.err" || { tail -20 "$D/c2k.err"; exit 1; }
+        python3 bench.py --full --no-cpu-baseline --config C2 --steps 60 --warmup 5 > "$D/c2k.json" 2> "$D/c2k.err" || { tail -20 "$D/c2k.err"; exit 1; }
       python3 tools/trace_eval.py "$D/c2k/run_kernel_trace.csv" "k_contract<8, 0, false, false, false" > "$D/c2_timeline.txt" && tail -1 "$D/c2_timeline.txt" ;;
     pmc)
       for ctr in "FETCH_SIZE" "WRITE_SIZE"; do
