@@ -25,7 +25,8 @@
  *   sgp_vi_phase1/2, sgp_vi_finish: the same VI evaluation split at its two
  *                      row-sum reductions so a caller can all-reduce across GPUs.
  *   sgp_eval_laplace <- newtrap_sparseGP (R/newtrap_sparseGP.R:6-186) + dlogq_dcov_par
- *                      (R/laplace_approx_gradient.R:25-553), Poisson likelihood
+ *                      (R/laplace_approx_gradient.R:25-553), Poisson likelihood or, after
+ *                      sgp_lap_set_family, Bernoulli
  *
  * Hyperparameters are passed as `theta` laid out [sigma, l_1..l_L, tau] with
  * L = 1 (sqexp, exp) or L = d (ard).  Gradients are d/d log(theta) in that order
@@ -115,8 +116,8 @@ int sgp_ctx_destroy(sgp_ctx* ctx);
  * devices by an in-process RCCL all-reduce (ncclCommInitAll over the distinct devices, on each
  * device's stream, in place).  A device may repeat (several shards on one GPU).
  * The handle is used with the ordinary entry points: sgp_eval_vi / sgp_eval_fitc /
- * sgp_eval_laplace / sgp_lap_nr, sgp_lap_set_f / sgp_lap_set_expo / sgp_lap_get_f /
- * sgp_lap_get_grad_psi (n values
+ * sgp_eval_laplace / sgp_lap_nr, sgp_lap_set_f / sgp_lap_set_expo / sgp_lap_set_family /
+ * sgp_lap_get_f / sgp_lap_get_grad_psi (n values
  * in the global row order) / sgp_lap_objective_values, sgp_posterior_u, sgp_ctx_enable_knot_grad,
  * sgp_knot_gradient (bounds NULL = the knot bounds of ALL rows), sgp_ctx_row_bounds (all rows),
  * sgp_ctx_set_data, sgp_ctx_rows (all rows), the three candidate scorers (each VI candidate as an
@@ -175,7 +176,8 @@ int sgp_fitc_phase2(sgp_ctx* ctx, const double* red1, int64_t n_global, unsigned
                     double* red2);
 int sgp_fitc_finish(sgp_ctx* ctx, const double* red2, double* obj, double* grad);
 
-/* Poisson sparse Laplace (config 5): one evaluation = newtrap_sparseGP warm-started from the
+/* Sparse Laplace (config 5; Poisson likelihood unless sgp_lap_set_family chose another): one
+ * evaluation = newtrap_sparseGP warm-started from the
  * context's latent vector f (R/newtrap_sparseGP.R:6-186, obj_fun_pois
  * R/laplace_approx_obj_funs.R:108-174) followed by dlogq_dcov_par at the mode
  * (R/laplace_approx_gradient.R:25-553), exactly as one iteration of laplace_grad_ascent
@@ -199,6 +201,26 @@ int sgp_lap_set_f(sgp_ctx* ctx, const double* f /* n host values, or NULL */, do
  * values in the global row order. */
 #define SGP_EXPO_ROWS 0.0
 int sgp_lap_set_expo(sgp_ctx* ctx, const double* a /* n host values, or NULL */, double fill);
+/* Likelihood family of the sparse Laplace path.  The setting is resident on the context (as
+ * the per-row exposure is; default SGP_FAM_POISSON) and honoured by sgp_eval_laplace,
+ * sgp_lap_nr, sgp_lap_begin / sgp_lap_step, sgp_lap_candidates, sgp_lap_get_grad_psi and
+ * sgp_posterior_u; a multi-device context forwards it to every shard.
+ * SGP_FAM_BERNOULLI is the reference's family = "bernoulli" (R/optimize_gp.R:570-665): the same
+ * newtrap_sparseGP / dlogq_dcov_par algebra with, for pi = 1/(1 + exp(-f)) and pi' = pi (1 - pi),
+ *   d1 = y (1 - pi) - pi + y pi        (R/derivative_functions_of_data_likelihoods.R:182)
+ *   W = d2 = (1 - 2 pi)(y - pi) - (y (1 - pi)^2 + pi^2 + y pi^2)       (l.108-109; the same in
+ *        obj_fun_bern, R/laplace_approx_obj_funs.R:225-226)
+ *   W3 = d3 = -2 pi' (y - pi) - pi' (1 - 2 pi) - (2 y (1 - pi)(-pi') + 2 pi pi' + 2 y pi pi')
+ *        (l.141-142)
+ *   log p = sum y plogis(f, log.p = TRUE) + (1 - y) plogis(-f, log.p = TRUE)
+ *        (obj_fun_bern, R/laplace_approx_obj_funs.R:209-210, 249-251)
+ * reproduced as written: for y = 1 that W is -pi - pi^2 rather than -pi (1 - pi) (DESIGN.md
+ * quirk Q19).  The exposure argument is validated as for Poisson but not read; the reference
+ * starts NR at f = 0 (R/optimize_gp.R:583).  Every response must be 0 or 1: SGP_EINVAL names the
+ * first that is not, checked here and whenever sgp_ctx_set_data replaces y under this family
+ * (not per evaluation); the family is left as it was.  An unknown family is SGP_EINVAL. */
+enum { SGP_FAM_POISSON = 0, SGP_FAM_BERNOULLI = 1 };
+int sgp_lap_set_family(sgp_ctx* ctx, int family);
 int sgp_lap_get_f(sgp_ctx* ctx, double* f /* n host values */);
 /* grad psi of the last Newton-Raphson step (n host values): the `gradient` element
  * newtrap_sparseGP returns (R/newtrap_sparseGP.R:183-184) -- evaluated at the mode estimate

@@ -23,6 +23,7 @@ SGP_FLAG_R_DET = 1
 SGP_FLAG_OBJ_ONLY = 2
 SGP_PRED_VI, SGP_PRED_LAPLACE, SGP_PRED_FULL = 0, 1, 2
 SGP_EXPO_ROWS = 0.0   # expo argument: the per-row exposure of sgp_lap_set_expo
+FAMILIES = {"poisson": 0, "bernoulli": 1}   # SGP_FAM_*: sgp_lap_set_family
 
 # name -> (restype, argtypes); exactly the functions declared in include/sgp.h
 PROTOTYPES = {
@@ -69,6 +70,7 @@ PROTOTYPES = {
     "sgp_fitc_finish": (C.c_int, [C.c_void_p, C.c_void_p, c_double_p, c_double_p]),
     "sgp_lap_set_f": (C.c_int, [C.c_void_p, c_double_p, C.c_double]),
     "sgp_lap_set_expo": (C.c_int, [C.c_void_p, c_double_p, C.c_double]),
+    "sgp_lap_set_family": (C.c_int, [C.c_void_p, C.c_int]),
     # include/sgp_diag.h (diagnostics: GPU tests and bench.py)
     "sgp_diag_gj_pair": (C.c_int, [C.c_int, C.c_int64, c_double_p, c_double_p, C.c_double, C.c_int,
                                    c_double_p, c_double_p, c_double_p]),

@@ -305,12 +305,15 @@ struct sgp_ctx {
   double* lm = nullptr;                   // LM_N x mp_max knot vectors
   double* lslab = nullptr;                // K^T V row-chunk partials
   double* Cprev = nullptr;                // (K22 + S_B)^-1 of the previous NR iterate
+  // refined m x m solves (lap_refine): A_Z = K22 + S_Z, A_B = K22 + S_B and two m-vectors
+  double *lapAZ = nullptr, *lapAB = nullptr, *laprv = nullptr;
   int64_t lslab_cap = 0;
   double* lred[2] = {nullptr, nullptr};   // ping-pong reduction buffers of sgp_eval_laplace
   int lap_state = 0, lap_it = 0, lap_maxit = 0;
   double lap_obj = 0.0, lap_obj_prev = 0.0, lap_cnt = 0.0, lap_tol = 0.0, lap_expo = 1.0;
   bool lap_expo_rows = false;             // LV_AEXP holds a per-row exposure (sgp_lap_set_expo)
   const double* lap_av = nullptr;         // this NR run's per-row exposure (nullptr: lap_expo)
+  int lap_family = SGP_FAM_POISSON;       // sgp_lap_set_family
   std::vector<double> lap_objs;           // objective_function_values of the last NR run
   // timing
   bool timing = false;
@@ -506,7 +509,8 @@ void ctx_free(sgp_ctx* c) {
                   c->sk_ws,  c->sk_flags,
                   c->Xt22,   c->T22,    c->dinv22, c->omega, c->pvec, c->rowq, c->red2f,
                   c->y,      c->mu,     c->lv,     c->lm,    c->lslab, c->lred[0], c->lred[1],
-                  c->Cprev,  c->knot_slab, c->knot_part, c->knot_kmm, c->tslab, c->tq, c->tp,
+                  c->Cprev,  c->lapAZ,  c->lapAB,  c->laprv,
+                  c->knot_slab, c->knot_part, c->knot_kmm, c->tslab, c->tq, c->tp,
                   c->rr_dev, c->Sfull, c->gjs, c->mmpart, c->rsync};
   for (void* p : ptrs)
     if (p) hipFree(p);
@@ -1045,6 +1049,8 @@ int sgp_ctx_set_stream(sgp_ctx* c, void* s) {
 int sgp_ctx_set_data(sgp_ctx* c, const double* y, const double* mu) {
   MULTI_FWD(c, y && mu ? multi_set_data(c->multi, y, mu) : multi_bad_args());
   if (!c || !y || !mu) { set_err("invalid arguments"); return SGP_EINVAL; }
+  if (c->lap_family == SGP_FAM_BERNOULLI && sgp_internal_check_bernoulli_y(y, c->n, 0))
+    return SGP_EINVAL;   // nothing replaced
   HIPCHK(hipSetDevice(c->device));
   std::vector<double> hr((size_t)c->n_pad, 0.0);
   for (int64_t i = 0; i < c->n; ++i) hr[(size_t)i] = y[i] - mu[i];
@@ -2013,6 +2019,42 @@ int sgp_lap_set_expo(sgp_ctx* c, const double* a, double fill) {
   return SGP_OK;
 }
 
+extern "C++" {   // sgp_multi.h hooks
+// family = "bernoulli" takes responses in {0, 1} (R/optimize_gp.R:570-665)
+int sgp_internal_check_bernoulli_y(const double* y, int64_t n, int64_t row0) {
+  for (int64_t i = 0; i < n; ++i)
+    if (!(y[i] == 0.0 || y[i] == 1.0)) {
+      set_err("Bernoulli family: response y[%lld] = %g is not 0 or 1", (long long)(row0 + i),
+              y[i]);
+      return SGP_EINVAL;
+    }
+  return SGP_OK;
+}
+
+// one shard's (or a one-device context's) family; row0 = its first row in the caller's y
+int sgp_internal_lap_set_family(sgp_ctx* c, int family, int64_t row0) {
+  if (!c) { set_err("context is NULL"); return SGP_EINVAL; }
+  if (family != SGP_FAM_POISSON && family != SGP_FAM_BERNOULLI) {
+    set_err("sgp_lap_set_family: unknown family %d", family);
+    return SGP_EINVAL;
+  }
+  if (family == SGP_FAM_BERNOULLI && c->lap_family != family) {
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<double> hy((size_t)c->n);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(hy.data(), c->y, sizeof(double) * hy.size(), hipMemcpyDeviceToHost));
+    if (sgp_internal_check_bernoulli_y(hy.data(), c->n, row0)) return SGP_EINVAL;
+  }
+  c->lap_family = family;   // from the next evaluation on; the last one's results stay readable
+  return SGP_OK;
+}
+}  // extern "C++"
+
+int sgp_lap_set_family(sgp_ctx* c, int family) {
+  MULTI_FWD(c, multi_lap_set_family(c->multi, family));
+  return sgp_internal_lap_set_family(c, family, 0);
+}
+
 int sgp_lap_get_grad_psi(sgp_ctx* c, double* out) {
   MULTI_FWD(c, out ? multi_lap_get_grad_psi(c->multi, out) : multi_bad_args());
   if (!c || !out) { set_err("invalid arguments"); return SGP_EINVAL; }
@@ -2037,14 +2079,44 @@ int sgp_lap_get_f(sgp_ctx* c, double* f) {
   return SGP_OK;
 }
 
+// The m x m systems are solved through explicit Gauss-Jordan inverses, and x = inv(A) b carries
+// an error of order cond(A) eps |inv(A)| |b|: with many knots per length scale (A_Z = K22 + S_Z
+// at condition 1e7, |t_Z| ~ 1e4) that reaches 1e-3 in x1 and 1e-5 in the mode.  One step of
+// iterative refinement, x += inv(A) (b - A x), brings it down to cond(A) eps |x|, what a
+// Cholesky solve gives.  It runs for the Bernoulli family, whose NR takes hundreds of slow steps
+// through such systems; the Poisson path keeps its solves, and so its results, as they were.
+static bool lap_refine(const sgp_ctx* c) { return c->lap_family == SGP_FAM_BERNOULLI; }
+
+static int lap_refine_ensure(sgp_ctx* c) {
+  if (c->lapAZ) return SGP_OK;
+  const int64_t mp = c->mp_max;
+  int st = dalloc(&c->lapAZ, mp * mp);
+  st = st ? st : dalloc(&c->lapAB, mp * mp);
+  st = st ? st : dalloc(&c->laprv, 2 * mp);
+  return st;
+}
+
+// x <- x + Ainv (b - A x)   (A, Ainv: mp x mp; b, x: mp)
+static int lap_refine_solve(sgp_ctx* c, const double* A, const double* Ainv, const double* b,
+                            double* x) {
+  const int64_t mp = c->mp;
+  double *r = c->laprv, *d = c->laprv + c->mp_max;
+  HIPCHK(dense_gemv(A, mp, x, 1.0, d, c->stream));
+  HIPCHK(dense_axpby(1.0, b, -1.0, d, r, mp, c->stream));
+  HIPCHK(dense_gemv(Ainv, mp, r, 1.0, d, c->stream));
+  HIPCHK(dense_axpby(1.0, x, 1.0, d, r, mp, c->stream));
+  HIPCHK(hipMemcpyAsync(x, r, sizeof(double) * mp, hipMemcpyDeviceToDevice, c->stream));
+  return SGP_OK;
+}
+
 // objective partials at the current f into red[o ..]: [S_B, t_Z, r'Z^-1 r, log p(y|f), log Z2]
 static int lap_obj_partials(sgp_ctx* c, double* red, int64_t o) {
   const int64_t mp = c->mp, mm = mp * mp;
   Scope t(c, "lap_obj");
   int nb = 0;
   HIPCHK(launch_lap_obj(c->n, c->n_pad, lvec(c, LV_F), c->y, c->mu, lvec(c, LV_Z),
-                        lvec(c, LV_ZI), c->lap_expo, c->lap_av, lvec(c, LV_B), lvec(c, LV_RF),
-                        lvec(c, LV_TV), c->slab_small, &nb, c->stream));
+                        lvec(c, LV_ZI), c->lap_expo, c->lap_av, c->lap_family, lvec(c, LV_B),
+                        lvec(c, LV_RF), lvec(c, LV_TV), c->slab_small, &nb, c->stream));
   HIPCHK(launch_syrk_aug(c->K, c->n_pad, mp, lvec(c, LV_RF), lvec(c, LV_B), c->slab_syrk,
                          c->slab_syrk_cap, red + o, c->stream, 3, lvec(c, LV_TV)));
   HIPCHK(launch_colsum(c->slab_small, nb, 2, red + o + mm + mp + 1, c->stream));
@@ -2137,6 +2209,14 @@ static int lap_consume_obj(sgp_ctx* c, const double* red, int64_t o, bool first,
                                  c->status + 2, c->gjs, c->stream));
     HIPCHK(launch_sum_small(c->logdB, mp / SGP_DB, c->sc + SC_LDB, c->stream));
     HIPCHK(dense_gemv(c->Bm, mp, red + o + mm, 1.0, lmv(c, LM_X1), c->stream));
+    if (lap_refine(c)) {
+      int st = lap_refine_ensure(c);
+      if (st) return st;
+      if (first) HIPCHK(dense_axpby(1.0, c->K22, 1.0, red, c->lapAZ, mm, c->stream));
+      HIPCHK(dense_axpby(1.0, c->K22, 1.0, red + o, c->lapAB, mm, c->stream));
+      st = lap_refine_solve(c, c->lapAZ, c->Bm, red + o + mm, lmv(c, LM_X1));
+      if (st) return st;
+    }
     HIPCHK(launch_dot(red + o + mm, lmv(c, LM_X1), mp, c->slab_small, c->sc + SC_TU, c->stream));
     HIPCHK(hipMemcpyAsync(c->sc + SC_RR, red + o + mm + mp, 3 * sizeof(double),
                           hipMemcpyDeviceToDevice, c->stream));
@@ -2198,7 +2278,8 @@ int sgp_lap_step(sgp_ctx* c, const double* red_in, double* red_out, int64_t* cou
         // one pass over K12: y1 = K x1, the row update and K^T v from the same staged rows
         HIPCHK(launch_lap_nr_a_fused(c->K, n, n_pad, mp, lmv(c, LM_X1), lvec(c, LV_F), c->y,
                                      c->mu, lvec(c, LV_Z), lvec(c, LV_ZI), c->lap_expo,
-                                     c->lap_av, c->lap_tol, lvec(c, LV_Y1), lvec(c, LV_G), lvec(c, LV_OMZW),
+                                     c->lap_av, c->lap_family, c->lap_tol, lvec(c, LV_Y1),
+                                     lvec(c, LV_G), lvec(c, LV_OMZW),
                                      lvec(c, LV_V), lvec(c, LV_GPSI), c->lslab, c->lslab_cap,
                                      red_out, red_out + mp, c->stream));
       } else {
@@ -2206,9 +2287,9 @@ int sgp_lap_step(sgp_ctx* c, const double* red_in, double* red_out, int64_t* cou
                                 c->stream));
         int nb = 0;
         HIPCHK(launch_lap_nr_a(n, n_pad, lvec(c, LV_F), c->y, c->mu, lvec(c, LV_Z),
-                               lvec(c, LV_ZI), c->lap_expo, c->lap_av, lvec(c, LV_Y1), c->lap_tol,
-                               lvec(c, LV_G), lvec(c, LV_OMZW), lvec(c, LV_V), lvec(c, LV_GPSI),
-                               c->slab_small, &nb, c->stream));
+                               lvec(c, LV_ZI), c->lap_expo, c->lap_av, c->lap_family,
+                               lvec(c, LV_Y1), c->lap_tol, lvec(c, LV_G), lvec(c, LV_OMZW),
+                               lvec(c, LV_V), lvec(c, LV_GPSI), c->slab_small, &nb, c->stream));
         HIPCHK(launch_gemv_cols(c->K, n_pad, mp, lvec(c, LV_V), n_pad, 1, c->lslab, c->lslab_cap,
                                 red_out, c->stream));
         HIPCHK(launch_colsum(c->slab_small, nb, 1, red_out + mp, c->stream));
@@ -2236,7 +2317,8 @@ int sgp_lap_step(sgp_ctx* c, const double* red_in, double* red_out, int64_t* cou
                               lvec(c, LV_ZI), lmv(c, LM_X1), lvec(c, LV_C2), c->rowq,
                               lvec(c, LV_P), c->stream, tstore_ready(c) ? c->tp : nullptr));
     HIPCHK(launch_lap_grad_a(n, n_pad, lvec(c, LV_F), c->y, c->mu, lvec(c, LV_Z), lvec(c, LV_ZI),
-                             c->lap_expo, c->lap_av, nullptr, lvec(c, LV_P), lvec(c, LV_C2),
+                             c->lap_expo, c->lap_av, c->lap_family, nullptr, lvec(c, LV_P),
+                             lvec(c, LV_C2),
                              lvec(c, LV_G), lvec(c, LV_B), lvec(c, LV_DMT), lvec(c, LV_SV),
                              lvec(c, LV_BSV), c->stream));
     HIPCHK(launch_gemv_cols(c->K, n_pad, mp, lvec(c, LV_C2), n_pad, 3, c->lslab, c->lslab_cap,
@@ -2255,6 +2337,10 @@ int sgp_lap_step(sgp_ctx* c, const double* red_in, double* red_out, int64_t* cou
       HIPCHK(hipMemcpyAsync(c->sc + SC_RR + 3, red_in + mp, sizeof(double),
                             hipMemcpyDeviceToDevice, c->stream));
       HIPCHK(dense_gemv(c->Binv, mp, red_in, 1.0, lmv(c, LM_X2), c->stream));
+      if (lap_refine(c)) {
+        int st = lap_refine_solve(c, c->lapAB, c->Binv, red_in, lmv(c, LM_X2));
+        if (st) return st;
+      }
       if (!fused) {
         HIPCHK(launch_gemv_rows(c->K, n_pad, mp, lmv(c, LM_X2), nullptr, lvec(c, LV_Y2),
                                 nullptr, c->stream));
@@ -2273,9 +2359,10 @@ int sgp_lap_step(sgp_ctx* c, const double* red_in, double* red_out, int64_t* cou
                                      red_out + mm, red_out + mm + mp, c->stream));
       int nb = 0;
       HIPCHK(launch_lap_obj(n, n_pad, lvec(c, LV_F), c->y, c->mu, lvec(c, LV_Z), lvec(c, LV_ZI),
-                            c->lap_expo, c->lap_av, lvec(c, LV_B), lvec(c, LV_RF), lvec(c, LV_TV),
-                            c->slab_small, &nb, c->stream));
-      // B = W / (Z W - 1) >= 0 (W = -a e^f <= 0, Z > 0)
+                            c->lap_expo, c->lap_av, c->lap_family, lvec(c, LV_B), lvec(c, LV_RF),
+                            lvec(c, LV_TV), c->slab_small, &nb, c->stream));
+      // B = W / (Z W - 1) >= 0 (Z > 0 and W <= 0: -a e^f, or the Bernoulli -pi (1 - pi) at
+      // y = 0 and -pi - pi^2 at y = 1)
       HIPCHK(launch_syrk_aug(c->K, n_pad, mp, lvec(c, LV_RF), lvec(c, LV_B), c->slab_syrk,
                              c->slab_syrk_cap, red_out, c->stream, 3, nullptr, 0, nullptr, false,
                              true));
@@ -2299,6 +2386,10 @@ int sgp_lap_step(sgp_ctx* c, const double* red_in, double* red_out, int64_t* cou
     HIPCHK(dense_gemv(c->K22inv, mp, ggr, 1.0, lmv(c, LM_GG), c->stream));
     HIPCHK(dense_gemv(c->K22inv, mp, ggr, -1.0, lmv(c, LM_NGG), c->stream));
     HIPCHK(dense_gemv(c->Binv, mp, w, 1.0, lmv(c, LM_CW), c->stream));
+    if (lap_refine(c)) {
+      int st = lap_refine_solve(c, c->lapAB, c->Binv, w, lmv(c, LM_CW));
+      if (st) return st;
+    }
     HIPCHK(launch_gemv_rows(c->K, n_pad, mp, lmv(c, LM_CW), nullptr, lvec(c, LV_Y2), nullptr,
                             c->stream));
     int nb = 0;

@@ -1,5 +1,6 @@
-// Per-row kernels of the Poisson sparse-Laplace path (newtrap_sparseGP + dlogq_dcov_par in
-// adjoint form) and the two HBM-bound K12 matrix-vector passes it needs.
+// Per-row kernels of the sparse-Laplace path (newtrap_sparseGP + dlogq_dcov_par in adjoint form,
+// DESIGN.md sec. 3.4; Poisson and Bernoulli likelihoods, LapLik below) and the two HBM-bound K12
+// matrix-vector passes it needs.
 //
 // Every kernel here is a single streaming pass: the n-vectors are ~8 B/row each, the GEMVs
 // read K12 (n_pad x mp, row-major) once.  Per-block partial sums go to a slab reduced by
@@ -11,10 +12,73 @@
 // helpers, "a vector of the areas of each grid cell", derivative_functions_of_data_likelihoods.R:
 // 38): W = d2 = d3 = -a e^f, d1 = y - a e^f.  a is per row: av[i] when the context holds a
 // per-row exposure (sgp_lap_set_expo), the scalar expo otherwise (av == nullptr).
+// The Bernoulli family (R/derivative_functions_of_data_likelihoods.R:86-235,
+// R/laplace_approx_obj_funs.R:189-341) runs the same rows with its own d1, W, W3 and log p.
+#include "../../include/sgp.h"
 #include "sgp_internal.h"
 #include "sgp_probe.h"
 
 namespace {
+
+// The data likelihood of one row: d1 = d log p / df, W = d2, W3 = d3 and the row's log p(y|f)
+// term, as the reference writes them.  Everything else in this file is family-free.
+template <int FAM>
+struct LapLik;
+
+// Poisson with exposure a (derivative_functions_of_data_likelihoods.R:7-61): W = W3 = -a e^f.
+// The expressions stand as the kernels held them before the families were split, so this
+// instantiation's results are unchanged.
+template <>
+struct LapLik<SGP_FAM_POISSON> {
+  double ai, e;
+  __device__ __forceinline__ LapLik(double fi, double /*yi*/, double a) : ai(a), e(exp(fi)) {}
+  __device__ __forceinline__ static double expo(const double* av, int64_t i, double ex) {
+    return av ? av[i] : ex;
+  }
+  __device__ __forceinline__ static double logexpo(const double* av, double ai, double lex) {
+    return av ? log(ai) : lex;
+  }
+  __device__ __forceinline__ double W() const { return -ai * e; }
+  __device__ __forceinline__ double W3() const { return -ai * e; }
+  __device__ __forceinline__ double d1(double yi) const { return -ai * e + yi; }
+  __device__ __forceinline__ double logp(double fi, double yi, double lai) const {
+    return yi * lai - lgamma(yi + 1.0) - ai * e + yi * fi;
+  }
+};
+
+// R's log1pexp (nmath/plogis.c, behind plogis(..., log.p = TRUE)): log(1 + e^x) without overflow
+__device__ __forceinline__ double log1pexp(double x) {
+  if (x <= 18.0) return log1p(exp(x));
+  if (x > 33.3) return x;
+  return x + exp(-x);
+}
+
+// Bernoulli with the logistic link, pi = 1/(1 + e^-f) (my_logistic, laplace_approx_obj_funs.R:
+// 178-183).  d1 l.182, W l.108-109 (= obj_fun_bern l.225-226), W3 l.141-142, log p
+// obj_fun_bern l.209-210, 249-251.  For y = 1 the reference's W is -pi - pi^2, not the true
+// -pi(1 - pi), and W3 is that W's derivative (quirk Q19): reproduced as written.
+// The exposure is not read.
+template <>
+struct LapLik<SGP_FAM_BERNOULLI> {
+  double pi, yi;
+  __device__ __forceinline__ LapLik(double fi, double y, double /*a*/)
+      : pi(1.0 / (1.0 + exp(-fi))), yi(y) {}
+  __device__ __forceinline__ static double expo(const double*, int64_t, double) { return 1.0; }
+  __device__ __forceinline__ static double logexpo(const double*, double, double) { return 0.0; }
+  __device__ __forceinline__ double W() const {
+    return (1.0 - 2.0 * pi) * (yi - pi) -
+           (yi * ((1.0 - pi) * (1.0 - pi)) + pi * pi + yi * (pi * pi));
+  }
+  __device__ __forceinline__ double W3() const {
+    const double dp = pi * (1.0 - pi);
+    return -2.0 * dp * (yi - pi) - dp * (1.0 - 2.0 * pi) -
+           (2.0 * yi * (1.0 - pi) * (-dp) + 2.0 * pi * dp + 2.0 * yi * pi * dp);
+  }
+  __device__ __forceinline__ double d1(double y) const { return y * (1.0 - pi) - pi + y * pi; }
+  __device__ __forceinline__ double logp(double fi, double y, double) const {
+    return y * -log1pexp(-fi) + (1.0 - y) * -log1pexp(fi);
+  }
+};
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -56,6 +120,7 @@ __global__ void __launch_bounds__(256) k_lap_z(const double* __restrict__ q, int
 // Objective row terms at f (laplace_approx_obj_funs.R:108-174): SYRK weights
 // B = 1/(Z - 1/W) (the R2/R3 weight: -W/Z2 = B), rf = f - mu, tv = rf/Z,
 // slab = [sum log p(y_i|f_i), sum log Z2_i],  Z2 = 1 + sqrt(-W) Z sqrt(-W).
+template <int FAM>
 __global__ void __launch_bounds__(256) k_lap_obj(int64_t n, int64_t n_pad,
                                                  const double* __restrict__ f,
                                                  const double* __restrict__ y,
@@ -70,14 +135,15 @@ __global__ void __launch_bounds__(256) k_lap_obj(int64_t n, int64_t n_pad,
   ROW_LOOP(i) {
     if (i < n) {
       const double fi = f[i], yi = y[i], zi = Z[i];
-      const double ai = av ? av[i] : expo, lai = av ? log(ai) : logexpo;
-      const double e = exp(fi);
-      const double W = -ai * e;
+      const double ai = LapLik<FAM>::expo(av, i, expo);
+      const double lai = LapLik<FAM>::logexpo(av, ai, logexpo);
+      const LapLik<FAM> lik(fi, yi, ai);
+      const double W = lik.W();
       B[i] = 1.0 / (zi - 1.0 / W);
       const double r = fi - mu[i];
       rf[i] = r;
       tv[i] = zinv[i] * r;
-      acc[0] += yi * lai - lgamma(yi + 1.0) - ai * e + yi * fi;
+      acc[0] += lik.logp(fi, yi, lai);
       const double sw = sqrt(-W);
       acc[1] += log(1.0 + sw * zi * sw);
     } else {
@@ -93,6 +159,7 @@ __global__ void __launch_bounds__(256) k_lap_obj(int64_t n, int64_t n_pad,
 //   g = y - a e^f, omzw = 1 - Z W, gpsi = g - (rf - y1)/Z   (y1 = K Bm_Z^-1 t_Z),
 //   v = gpsi / omzw (input of the K^T pass), slab = [#{|gpsi_i| > tol}]; gpsi itself is kept
 //   (newtrap_sparseGP's returned `gradient`, R/newtrap_sparseGP.R:178-185).
+template <int FAM>
 __global__ void __launch_bounds__(256) k_lap_nr_a(int64_t n, int64_t n_pad,
                                                   const double* __restrict__ f,
                                                   const double* __restrict__ y,
@@ -108,10 +175,10 @@ __global__ void __launch_bounds__(256) k_lap_nr_a(int64_t n, int64_t n_pad,
   double acc[1] = {0.0};
   ROW_LOOP(i) {
     if (i < n) {
-      const double ai = av ? av[i] : expo;
-      const double e = exp(f[i]);
-      const double W = -ai * e;
-      const double gi = -ai * e + y[i];
+      const double ai = LapLik<FAM>::expo(av, i, expo);
+      const LapLik<FAM> lik(f[i], y[i], ai);
+      const double W = lik.W();
+      const double gi = lik.d1(y[i]);
       const double zi = Z[i], iz = zinv[i];
       const double om = 1.0 - zi * W;
       const double gp = gi + (-iz * (f[i] - mu[i]) + iz * y1[i]);
@@ -155,6 +222,7 @@ __global__ void __launch_bounds__(256) k_lap_nr_b(int64_t n, int64_t n_pad,
 // Gradient rows, part a (laplace_approx_gradient.R:133-178): with p_i = k_i^T C k_i,
 //   c2 = rf/Z - y1/Z (left as passed in when y1 == nullptr), B = 1/(Z - 1/W), dMt = B - B^2 p  (diag of Sigma~^-1),
 //   comp4 = -1/D + (1/(Z D))^2 p  (D = W - 1/Z),  sv = comp4 (-W3)(-1/W),  bsv = B sv.
+template <int FAM>
 __global__ void __launch_bounds__(256) k_lap_grad_a(int64_t n, int64_t n_pad,
                                                     const double* __restrict__ f,
                                                     const double* __restrict__ y,
@@ -172,14 +240,14 @@ __global__ void __launch_bounds__(256) k_lap_grad_a(int64_t n, int64_t n_pad,
                                                     double* __restrict__ bsv) {
   ROW_LOOP(i) {
     if (i < n) {
-      const double ai = av ? av[i] : expo;
-      const double e = exp(f[i]);
-      const double W = -ai * e, W3 = W;
+      const double ai = LapLik<FAM>::expo(av, i, expo);
+      const LapLik<FAM> lik(f[i], y[i], ai);
+      const double W = lik.W(), W3 = lik.W3();
       const double zi = Z[i], iz = zinv[i];
       const double bi = 1.0 / (zi - 1.0 / W);
       const double pi = p[i];
       if (y1) c2[i] = iz * (f[i] - mu[i]) - iz * y1[i];   // else c2 came with p (fused alpha)
-      g[i] = -ai * e + y[i];
+      g[i] = lik.d1(y[i]);
       B[i] = bi;
       dMt[i] = bi - bi * bi * pi;
       const double D = W - 1.0 / zi;
@@ -331,7 +399,7 @@ struct LapPassArgs {
 // at C5, profiles/r4/lap_rowstream_ab.txt).  The four
 // waves' column sums are combined in fixed order at the end.  NQM: double2 columns per lane per
 // row (mp / 128 rounded up to 2, 4, 8 or 16), RF rows in flight per wave, OCC waves per SIMD.
-template <int MODE, int NQM, int RF, int OCC>
+template <int MODE, int FAM, int NQM, int RF, int OCC>
 __global__ void __launch_bounds__(256, OCC) k_lap_rowstream(const double* __restrict__ K, int64_t n,
                                                             int64_t n_pad, int64_t mp,
                                                             int64_t chunk, LapPassArgs pa) {
@@ -382,10 +450,10 @@ __global__ void __launch_bounds__(256, OCC) k_lap_rowstream(const double* __rest
         if (im < n) {
           const double fi = pa.f[im], yi = pa.y[im], mui = pa.mu[im], zi = pa.Z[im];
           const double iz = pa.zinv[im];
-          const double ai = pa.av ? pa.av[im] : pa.expo;
-          const double e = exp(fi);
-          const double W = -ai * e;
-          const double gi = -ai * e + yi;
+          const double ai = LapLik<FAM>::expo(pa.av, im, pa.expo);
+          const LapLik<FAM> lik(fi, yi, ai);
+          const double W = lik.W();
+          const double gi = lik.d1(yi);
           const double om = 1.0 - zi * W;
           const double gp = gi + (-iz * (fi - mui) + iz * dme);
           vme = (1.0 / om) * gp;
@@ -555,24 +623,32 @@ hipError_t launch_lap_z(const double* q, int64_t n, int64_t n_pad, double c0, do
 
 hipError_t launch_lap_obj(int64_t n, int64_t n_pad, const double* f, const double* y,
                           const double* mu, const double* Z, const double* zinv, double expo,
-                          const double* av, double* B, double* rf, double* tv, double* slab,
-                          int* nblocks, hipStream_t s) {
+                          const double* av, int fam, double* B, double* rf, double* tv,
+                          double* slab, int* nblocks, hipStream_t s) {
   const int nb = row_blocks(n_pad);
   *nblocks = nb;
-  hipLaunchKernelGGL(k_lap_obj, dim3(nb), dim3(256), 0, s, n, n_pad, f, y, mu, Z, zinv, expo,
-                     av ? 0.0 : log(expo), av, B, rf, tv, slab);
+  if (fam == SGP_FAM_BERNOULLI)
+    hipLaunchKernelGGL(k_lap_obj<SGP_FAM_BERNOULLI>, dim3(nb), dim3(256), 0, s, n, n_pad, f, y, mu,
+                       Z, zinv, 1.0, 0.0, nullptr, B, rf, tv, slab);
+  else
+    hipLaunchKernelGGL(k_lap_obj<SGP_FAM_POISSON>, dim3(nb), dim3(256), 0, s, n, n_pad, f, y, mu,
+                       Z, zinv, expo, av ? 0.0 : log(expo), av, B, rf, tv, slab);
   return hipGetLastError();
 }
 
 hipError_t launch_lap_nr_a(int64_t n, int64_t n_pad, const double* f, const double* y,
                            const double* mu, const double* Z, const double* zinv, double expo,
-                           const double* av, const double* y1, double tol, double* g,
+                           const double* av, int fam, const double* y1, double tol, double* g,
                            double* omzw, double* v, double* gpsi, double* slab, int* nblocks,
                            hipStream_t s) {
   const int nb = row_blocks(n_pad);
   *nblocks = nb;
-  hipLaunchKernelGGL(k_lap_nr_a, dim3(nb), dim3(256), 0, s, n, n_pad, f, y, mu, Z, zinv, expo, av,
-                     y1, tol, g, omzw, v, gpsi, slab);
+  if (fam == SGP_FAM_BERNOULLI)
+    hipLaunchKernelGGL(k_lap_nr_a<SGP_FAM_BERNOULLI>, dim3(nb), dim3(256), 0, s, n, n_pad, f, y,
+                       mu, Z, zinv, 1.0, nullptr, y1, tol, g, omzw, v, gpsi, slab);
+  else
+    hipLaunchKernelGGL(k_lap_nr_a<SGP_FAM_POISSON>, dim3(nb), dim3(256), 0, s, n, n_pad, f, y, mu,
+                       Z, zinv, expo, av, y1, tol, g, omzw, v, gpsi, slab);
   return hipGetLastError();
 }
 
@@ -590,7 +666,7 @@ int64_t lap_rowpass_slab(int64_t n_pad, int64_t mp) {
 }
 
 namespace {
-template <int MODE>
+template <int MODE, int FAM>
 hipError_t launch_rowpass(const double* K, int64_t n, int64_t n_pad, int64_t mp, LapPassArgs pa,
                           double* part, int64_t part_cap, double* out_t, double* out_sc,
                           hipStream_t s) {
@@ -609,10 +685,10 @@ hipError_t launch_rowpass(const double* K, int64_t n, int64_t n_pad, int64_t mp,
     constexpr int C = SGP_LAP_RS_CFG;
     constexpr int F2 = C == 1 ? 4 : C == 2 ? 16 : 8, O2 = C == 1 ? 4 : C == 2 ? 2 : 3;
     constexpr int F4 = C == 1 ? 2 : C == 2 ? 8 : 4, O4 = O2;
-    if (nq <= 2) hipLaunchKernelGGL((k_lap_rowstream<MODE, 2, F2, O2>), g, b, shm, s, K, n, n_pad, mp, chunk, pa);
-    else if (nq <= 4) hipLaunchKernelGGL((k_lap_rowstream<MODE, 4, F4, O4>), g, b, shm, s, K, n, n_pad, mp, chunk, pa);
-    else if (nq <= 8) hipLaunchKernelGGL((k_lap_rowstream<MODE, 8, 2, 2>), g, b, shm, s, K, n, n_pad, mp, chunk, pa);
-    else hipLaunchKernelGGL((k_lap_rowstream<MODE, 16, 1, 2>), g, b, shm, s, K, n, n_pad, mp, chunk, pa);
+    if (nq <= 2) hipLaunchKernelGGL((k_lap_rowstream<MODE, FAM, 2, F2, O2>), g, b, shm, s, K, n, n_pad, mp, chunk, pa);
+    else if (nq <= 4) hipLaunchKernelGGL((k_lap_rowstream<MODE, FAM, 4, F4, O4>), g, b, shm, s, K, n, n_pad, mp, chunk, pa);
+    else if (nq <= 8) hipLaunchKernelGGL((k_lap_rowstream<MODE, FAM, 8, 2, 2>), g, b, shm, s, K, n, n_pad, mp, chunk, pa);
+    else hipLaunchKernelGGL((k_lap_rowstream<MODE, FAM, 16, 1, 2>), g, b, shm, s, K, n, n_pad, mp, chunk, pa);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
@@ -625,14 +701,21 @@ hipError_t launch_rowpass(const double* K, int64_t n, int64_t n_pad, int64_t mp,
 hipError_t launch_lap_nr_a_fused(const double* K, int64_t n, int64_t n_pad, int64_t mp,
                                  const double* x1, const double* f, const double* y,
                                  const double* mu, const double* Z, const double* zinv,
-                                 double expo, const double* av, double tol, double* y1, double* g,
-                                 double* omzw, double* v, double* gpsi, double* part,
+                                 double expo, const double* av, int fam, double tol, double* y1,
+                                 double* g, double* omzw, double* v, double* gpsi, double* part,
                                  int64_t part_cap, double* out, double* out_cnt, hipStream_t s) {
   LapPassArgs pa{};
   pa.x = x1; pa.f = f; pa.y = y; pa.mu = mu; pa.Z = Z; pa.zinv = zinv;
   pa.expo = expo; pa.av = av; pa.tol = tol;
   pa.y1 = y1; pa.g = g; pa.omzw = omzw; pa.v = v; pa.gpsi = gpsi;
-  return launch_rowpass<LAP_PASS_A>(K, n, n_pad, mp, pa, part, part_cap, out, out_cnt, s);
+  if (fam == SGP_FAM_BERNOULLI) {
+    pa.expo = 1.0;
+    pa.av = nullptr;
+    return launch_rowpass<LAP_PASS_A, SGP_FAM_BERNOULLI>(K, n, n_pad, mp, pa, part, part_cap, out,
+                                                         out_cnt, s);
+  }
+  return launch_rowpass<LAP_PASS_A, SGP_FAM_POISSON>(K, n, n_pad, mp, pa, part, part_cap, out,
+                                                     out_cnt, s);
 }
 
 hipError_t launch_lap_nr_b_t_fused(const double* K, int64_t n, int64_t n_pad, int64_t mp,
@@ -645,7 +728,9 @@ hipError_t launch_lap_nr_b_t_fused(const double* K, int64_t n, int64_t n_pad, in
   pa.x = x2; pa.f = f; pa.f_out = f; pa.y = y; pa.mu = mu; pa.Z = Z; pa.zinv = zinv;
   pa.g_in = g; pa.omzw_in = omzw; pa.y1_in = y1;
   double* out_sc = out_rr;
-  return launch_rowpass<LAP_PASS_B>(K, n, n_pad, mp, pa, part, part_cap, out_t, out_sc, s);
+  // pass B holds no likelihood term: one instantiation serves every family
+  return launch_rowpass<LAP_PASS_B, SGP_FAM_POISSON>(K, n, n_pad, mp, pa, part, part_cap, out_t,
+                                                     out_sc, s);
 }
 
 hipError_t launch_lap_nr_b(int64_t n, int64_t n_pad, double* f, const double* mu, const double* Z,
@@ -658,11 +743,16 @@ hipError_t launch_lap_nr_b(int64_t n, int64_t n_pad, double* f, const double* mu
 
 hipError_t launch_lap_grad_a(int64_t n, int64_t n_pad, const double* f, const double* y,
                              const double* mu, const double* Z, const double* zinv, double expo,
-                             const double* av, const double* y1, const double* p, double* c2,
-                             double* g, double* B, double* dMt, double* sv, double* bsv,
-                             hipStream_t s) {
-  hipLaunchKernelGGL(k_lap_grad_a, dim3(row_blocks(n_pad)), dim3(256), 0, s, n, n_pad, f, y, mu,
-                     Z, zinv, expo, av, y1, p, c2, g, B, dMt, sv, bsv);
+                             const double* av, int fam, const double* y1, const double* p,
+                             double* c2, double* g, double* B, double* dMt, double* sv,
+                             double* bsv, hipStream_t s) {
+  const dim3 grid(row_blocks(n_pad));
+  if (fam == SGP_FAM_BERNOULLI)
+    hipLaunchKernelGGL(k_lap_grad_a<SGP_FAM_BERNOULLI>, grid, dim3(256), 0, s, n, n_pad, f, y, mu,
+                       Z, zinv, 1.0, nullptr, y1, p, c2, g, B, dMt, sv, bsv);
+  else
+    hipLaunchKernelGGL(k_lap_grad_a<SGP_FAM_POISSON>, grid, dim3(256), 0, s, n, n_pad, f, y, mu,
+                       Z, zinv, expo, av, y1, p, c2, g, B, dMt, sv, bsv);
   return hipGetLastError();
 }
 

@@ -134,6 +134,7 @@ struct MultiCtx {
   int64_t n = 0, m_max = 0, cap = 0;
   int d = 0;
   bool knot_on = false;
+  int lap_family = SGP_FAM_POISSON;   // every shard's family (sgp_lap_set_family)
   std::vector<double> xmin, xmax;   // column ranges of all rows
   // the host workers (sgp_pool.h: one per distinct device, barriers with votes, the job bodies)
   std::unique_ptr<sgp_pool::Pool> pool;
@@ -404,6 +405,9 @@ int multi_shards(const MultiCtx* mc, int* nshards, int* ndevices) {
 sgp_ctx* multi_lead(MultiCtx* mc) { return mc->shards[0].ctx; }
 
 int multi_set_data(MultiCtx* mc, const double* y, const double* mu) {
+  // every response is checked before any shard changes
+  if (mc->lap_family == SGP_FAM_BERNOULLI && sgp_internal_check_bernoulli_y(y, mc->n, 0))
+    return SGP_EINVAL;
   for (Shard& s : mc->shards) {
     const int st = sgp_ctx_set_data(s.ctx, y + s.row0, mu + s.row0);
     if (st) return st;
@@ -557,6 +561,21 @@ int multi_lap_set_expo(MultiCtx* mc, const double* a, double fill) {
     const int st = sgp_lap_set_expo(s.ctx, a ? a + s.row0 : nullptr, fill);
     if (st) return st;
   }
+  return SGP_OK;
+}
+
+// every shard takes the family or none does: a shard that refuses (a response that is not 0 or
+// 1) sends the shards before it back to the family they had
+int multi_lap_set_family(MultiCtx* mc, int family) {
+  for (size_t k = 0; k < mc->shards.size(); ++k) {
+    const int st = sgp_internal_lap_set_family(mc->shards[k].ctx, family, mc->shards[k].row0);
+    if (st) {
+      for (size_t j = 0; j < k; ++j)
+        (void)sgp_internal_lap_set_family(mc->shards[j].ctx, mc->lap_family, mc->shards[j].row0);
+      return st;
+    }
+  }
+  mc->lap_family = family;
   return SGP_OK;
 }
 

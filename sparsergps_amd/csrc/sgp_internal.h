@@ -330,11 +330,11 @@ hipError_t launch_lap_z(const double* q, int64_t n, int64_t n_pad, double c0, do
                         double* zinv, hipStream_t s);
 hipError_t launch_lap_obj(int64_t n, int64_t n_pad, const double* f, const double* y,
                           const double* mu, const double* Z, const double* zinv, double expo,
-                          const double* av, double* B, double* rf, double* tv, double* slab,
-                          int* nblocks, hipStream_t s);
+                          const double* av, int fam, double* B, double* rf, double* tv,
+                          double* slab, int* nblocks, hipStream_t s);
 hipError_t launch_lap_nr_a(int64_t n, int64_t n_pad, const double* f, const double* y,
                            const double* mu, const double* Z, const double* zinv, double expo,
-                           const double* av, const double* y1, double tol, double* g,
+                           const double* av, int fam, const double* y1, double tol, double* g,
                            double* omzw, double* v, double* gpsi, double* slab, int* nblocks,
                            hipStream_t s);
 // NR part a as one K pass (y1 = K x1, the row update above, out = K^T v, out_cnt = stop-rule
@@ -342,8 +342,8 @@ hipError_t launch_lap_nr_a(int64_t n, int64_t n_pad, const double* f, const doub
 hipError_t launch_lap_nr_a_fused(const double* K, int64_t n, int64_t n_pad, int64_t mp,
                                  const double* x1, const double* f, const double* y,
                                  const double* mu, const double* Z, const double* zinv,
-                                 double expo, const double* av, double tol, double* y1, double* g,
-                                 double* omzw, double* v, double* gpsi, double* part,
+                                 double expo, const double* av, int fam, double tol, double* y1,
+                                 double* g, double* omzw, double* v, double* gpsi, double* part,
                                  int64_t part_cap, double* out, double* out_cnt, hipStream_t s);
 // NR part b + the next objective's t as one K pass: f updated in place (y2 = K x2), out_t =
 // K^T tv and out_rr = sum tv (f - mu) at the new f, tv = (f - mu)/Z.  mp <= 2048.
@@ -360,9 +360,9 @@ hipError_t launch_lap_nr_b(int64_t n, int64_t n_pad, double* f, const double* mu
                            const double* y2, hipStream_t s);
 hipError_t launch_lap_grad_a(int64_t n, int64_t n_pad, const double* f, const double* y,
                              const double* mu, const double* Z, const double* zinv, double expo,
-                             const double* av, const double* y1, const double* p, double* c2,
-                             double* g, double* B, double* dMt, double* sv, double* bsv,
-                             hipStream_t s);
+                             const double* av, int fam, const double* y1, const double* p,
+                             double* c2, double* g, double* B, double* dMt, double* sv,
+                             double* bsv, hipStream_t s);
 hipError_t launch_lap_grad_b(int64_t n, int64_t n_pad, const double* B, const double* sv,
                              const double* y3, const double* dMt, const double* c2,
                              const double* g, double* h, double* a, double* slab, int* nblocks,

@@ -19,6 +19,8 @@ void sgp_internal_set_err(const char* msg);
 void sgp_internal_forget_eval(sgp_ctx* c);   // no posterior / grad psi after candidate scoring
 hipStream_t sgp_internal_stream(sgp_ctx* c);  // the context's launch stream
 int sgp_internal_share_streams(sgp_ctx* c, sgp_ctx* src);   // c uses src's three streams
+int sgp_internal_check_bernoulli_y(const double* y, int64_t n, int64_t row0);   // all in {0, 1}
+int sgp_internal_lap_set_family(sgp_ctx* c, int family, int64_t row0);
 
 int multi_create(MultiCtx** out, const int* devices, int nshards, const double* X, int64_t n,
                  int64_t ldx, int d, const double* y, const double* mu, int64_t m_max);
@@ -36,6 +38,7 @@ int multi_eval_laplace(MultiCtx* mc, int kernel, const double* theta, const doub
                        unsigned flags, double* obj, double* grad, int* nr_iters);
 int multi_lap_set_f(MultiCtx* mc, const double* f, double fill);
 int multi_lap_set_expo(MultiCtx* mc, const double* a, double fill);
+int multi_lap_set_family(MultiCtx* mc, int family);
 int multi_lap_get_f(MultiCtx* mc, double* f);
 int multi_lap_get_grad_psi(MultiCtx* mc, double* out);
 int multi_enable_knot_grad(MultiCtx* mc, int enable);

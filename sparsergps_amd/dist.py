@@ -132,6 +132,9 @@ class HipRowBackend:
         self._cur = 0
         return self.red1[:cnt]
 
+    def lap_set_family(self, family):
+        self.ctx.lap_set_family(family)
+
     def lap_step(self, red):
         bufs = (self.red1, self.red2)
         src, dst = bufs[self._cur], bufs[self._cur ^ 1]
@@ -187,7 +190,8 @@ class RowShardedVI:
 
 
 class RowShardedLaplace:
-    """Poisson sparse-Laplace evaluation (NR to the mode + gradient) over row blocks.
+    """Sparse-Laplace evaluation (NR to the mode + gradient) over row blocks, for the Poisson
+    (default) or Bernoulli family.
 
     The NR loop is the reference's (R/newtrap_sparseGP.R:76-131); each iteration has two
     exchange steps -- K^T (grad_psi / (1 - Z W)) with the stop-rule count (m + 1 doubles) and
@@ -206,11 +210,17 @@ class RowShardedLaplace:
             raise RuntimeError("force_collectives needs an initialised torch.distributed group")
         self.collective = self.world > 1 or force
 
-    def eval(self, theta, U, delta=1e-6, expo=1.0, tol=1e-5, maxit=1000):
+    def eval(self, theta, U, delta=1e-6, expo=1.0, tol=1e-5, maxit=1000, family="poisson"):
         """-> (objective, gradient d/dlog theta, NR iteration count).  expo: the Poisson
         exposure, a scalar or THIS rank's rows of a per-row exposure (the reference's `m` as a
-        vector of cell areas, R/derivative_functions_of_data_likelihoods.R:38)."""
+        vector of cell areas, R/derivative_functions_of_data_likelihoods.R:38); not read under
+        family="bernoulli".  The family is set on this rank's context on every call; every rank
+        passes the same one."""
         b = self.backend
+        if hasattr(b, "lap_set_family"):
+            b.lap_set_family(family)
+        elif family != "poisson":
+            raise ValueError(f"this backend has no lap_set_family (family={family!r})")
         with (b.stream_context() if hasattr(b, "stream_context") else contextlib.nullcontext()):
             red = b.lap_begin(theta, U, delta, expo, tol, maxit)
             while True:

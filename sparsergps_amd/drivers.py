@@ -2,7 +2,7 @@
 
   norm_grad_ascent_vi  R/vi_functions.R:606-1218             (Titsias VI)
   norm_grad_ascent     R/laplace_gradient_ascent.R:1111-1693  (FITC)
-  laplace_grad_ascent  R/laplace_gradient_ascent.R:10-623     (Poisson sparse Laplace)
+  laplace_grad_ascent  R/laplace_gradient_ascent.R:10-623     (Poisson / Bernoulli sparse Laplace)
 
 The loop itself is host logic (a few vector operations per iteration); every iteration body --
 the two K builds, the objective and the gradient the reference computes separately
@@ -211,11 +211,14 @@ def norm_grad_ascent(cov_par_start, cov_fun, dcov_fun_dtheta=True, dcov_fun_dkno
 
 def laplace_grad_ascent(cov_par_start, cov_fun, dcov_fun_dtheta=True, dcov_fun_dknot=None,
                         knot_opt=None, xu=None, xy=None, y=None, ff=None, mu=None, muu=None,
-                        m=1.0, opt=None, verbose=False, ctx=None):
-    """R/laplace_gradient_ascent.R:10-623 for the Poisson likelihood: every iteration is
-    newtrap_sparseGP warm-started from the previous mode (resident on the device) followed by
-    dlogq_dcov_par at the new mode, as one fused evaluation (sgp_eval_laplace)."""
+                        m=1.0, opt=None, verbose=False, ctx=None, family="poisson"):
+    """R/laplace_gradient_ascent.R:10-623 for the Poisson (default) or Bernoulli likelihood:
+    every iteration is newtrap_sparseGP warm-started from the previous mode (resident on the
+    device) followed by dlogq_dcov_par at the new mode, as one fused evaluation
+    (sgp_eval_laplace).  family="bernoulli" does not read m and needs mu."""
     o = _opts(opt, {"maxit_nr": 1000, "tol_nr": 1e-6})
+    if mu is None and family != "poisson":
+        raise ValueError(f'mu=None is a Poisson convention; pass mu with family="{family}"')
     y = np.asarray(y, dtype=np.float64).reshape(-1)
     xy_m = np.asarray(xy, dtype=np.float64).reshape(len(y), -1)
     d = xy_m.shape[1]
@@ -225,6 +228,7 @@ def laplace_grad_ascent(cov_par_start, cov_fun, dcov_fun_dtheta=True, dcov_fun_d
     kind = knot_fun_kind(dcov_fun_dknot)
     if ctx is None:
         ctx = SparseGPContext(xy_m, y, mu, m_max=xu.shape[0])
+    ctx.lap_set_family(family)
     ctx.enable_knot_grad(kind is not None)
     ctx.lap_set_f(ff)
     bounds = knot_bounds(xy_m)

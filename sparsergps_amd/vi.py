@@ -252,6 +252,19 @@ class SparseGPContext:
                 raise ValueError(f"exposure has {a.size} values for {self.n} rows")
             _lib.check(self._lib.sgp_lap_set_expo(self.handle, _lib.dptr(a), 0.0))
 
+    def lap_set_family(self, family="poisson"):
+        """Resident likelihood family of the Laplace entry points: "poisson" (the default of a
+        new context) or "bernoulli" (R/optimize_gp.R:570-665; every response must be 0 or 1,
+        else SGPError).  Stays set until changed."""
+        if family not in _lib.FAMILIES:
+            raise ValueError(f"family must be one of {sorted(_lib.FAMILIES)}, not {family!r}")
+        if not hasattr(self._lib, "sgp_lap_set_family"):
+            # an A/B library of an older revision (_lib.lib()): Poisson is the only family it has
+            if family == "poisson":
+                return
+            raise RuntimeError("this libsgp.so has no sgp_lap_set_family")
+        _lib.check(self._lib.sgp_lap_set_family(self.handle, _lib.FAMILIES[family]))
+
     def _expo(self, expo):
         """The expo argument of the Laplace entry points: a scalar as is; an n-vector is made
         resident (sgp_lap_set_expo) and passed as SGP_EXPO_ROWS.  A length-1 vector is the

@@ -1,6 +1,6 @@
 """Synthetic workloads of SURVEY.md 8(d) (numpy PCG64 streams): C2, C3 (C4 = C3 row-sharded)
-and C5.  Data generation only -- used by bench.py, the tests and tools; no reference files are
-read and nothing here computes a GP quantity.
+and C5, and a Bernoulli classification problem.  Data generation only -- used by bench.py, the
+tests and tools; no reference files are read and nothing here computes a GP quantity.
 """
 from __future__ import annotations
 
@@ -64,3 +64,19 @@ def make_poisson_problem(n=None, m=None, per_row_exposure=False):
     f0 = math.log(y.mean()) - np.log(a) * np.ones(n)
     cov_par = OrderedDict([("sigma", 1.0), ("l", 2.0), ("tau", 0.1)])
     return dict(X=X, U=U, y=y, mu=mu, f0=f0, a=a, cov_par=cov_par, cov_fun="sqexp", delta=1e-6)
+
+
+def make_bernoulli_problem(n, m, d=2, seed=11, cov_par=None):
+    """Bernoulli (classification) sparse Laplace, after the reference's classification vignette:
+    X and U uniform on (0, 10)^d, f = 2 sum_c sin(x_c) / sqrt(d), y ~ Bernoulli(logistic(f)),
+    mu = 0, f0 = 0 (R/optimize_gp.R:583), sqexp with the vignette's theta = (sigma=5, l=2,
+    tau=0.1) unless cov_par overrides it.  One PCG64 stream (`seed`) draws X, U and y in turn."""
+    g = _rng(seed)
+    X = g.uniform(0.0, 10.0, size=(n, d))
+    U = g.uniform(0.0, 10.0, size=(m, d))
+    f = 2.0 * np.sin(X).sum(axis=1) / math.sqrt(d)
+    y = (g.uniform(size=n) < 1.0 / (1.0 + np.exp(-f))).astype(np.float64)
+    if cov_par is None:
+        cov_par = OrderedDict([("sigma", 5.0), ("l", 2.0), ("tau", 0.1)])
+    return dict(X=X, U=U, y=y, mu=np.zeros(n), f0=np.zeros(n), cov_par=OrderedDict(cov_par),
+                cov_fun="sqexp", delta=1e-6)

@@ -1,0 +1,273 @@
+"""CPU restatement (numpy, fp64) of the reference's Bernoulli sparse-Laplace path, line by line:
+
+  d{1,2,3}log_py_dff_bern   R/derivative_functions_of_data_likelihoods.R:86-184
+  grad_loglik_fn_bern       R/derivative_functions_of_data_likelihoods.R:186-235
+  obj_fun_bern              R/laplace_approx_obj_funs.R:189-341
+  newtrap_sparseGP          R/newtrap_sparseGP.R:6-186 (+ _update 234-325) with those helpers
+  dlogq_dcov_par            R/laplace_approx_gradient.R:25-336 with those helpers (knots fixed)
+
+The matrix algebra is the Poisson path's and comes from oracle.sgp_oracle (laplace_mats, r_chol,
+r_solve, _dmats, a1_diag, _gaussian_comps, laplace_posterior_u); only the four likelihood
+helpers and the objective's log p(y|f) term are new.  They are restated as written, including
+the reference's W for y = 1 (-pi - pi^2, not -pi (1 - pi)).
+"""
+from __future__ import annotations
+
+import math
+from collections import OrderedDict
+
+import numpy as np
+
+from oracle import sgp_oracle as O
+
+
+def my_logistic(x):
+    """laplace_approx_obj_funs.R:178-183."""
+    return 1 / (1 + np.exp(-x))
+
+
+def log1pexp(x):
+    """R's log1pexp (nmath/plogis.c): log(1 + e^x), piecewise so that it never overflows."""
+    x = np.asarray(x, dtype=np.float64)
+    small = np.minimum(x, 18.0)
+    mid = x + np.exp(-np.maximum(x, 18.0))     # read only where 18 < x <= 33.3
+    return np.where(x <= 18.0, np.log1p(np.exp(small)), np.where(x > 33.3, x, mid))
+
+
+def plogis_log(q):
+    """plogis(q, log.p = TRUE) = -log1pexp(-q)."""
+    return -log1pexp(-np.asarray(q, dtype=np.float64))
+
+
+def dlog_py_dff_bern(ff, y):
+    """derivative_functions_of_data_likelihoods.R:165-184 (l.182)."""
+    pi_ff = my_logistic(ff)
+    return y * (1 - pi_ff) - pi_ff + y * pi_ff
+
+
+def d2log_py_dff_bern(ff, y):
+    """derivative_functions_of_data_likelihoods.R:90-112 (l.108-109)."""
+    pi_ff = my_logistic(ff)
+    return (1 - 2 * pi_ff) * (y - pi_ff) - (y * (1 - pi_ff) ** 2 + pi_ff ** 2 + y * pi_ff ** 2)
+
+
+def d3log_py_dff_bern(ff, y):
+    """derivative_functions_of_data_likelihoods.R:116-145 (l.141-142)."""
+    pi_ff = my_logistic(ff)
+    dpi_dff = pi_ff * (1 - pi_ff)
+    return (-2 * dpi_dff * (y - pi_ff) - dpi_dff * (1 - 2 * pi_ff) -
+            (2 * y * (1 - pi_ff) * (-dpi_dff) + 2 * pi_ff * dpi_dff + 2 * y * pi_ff * dpi_dff))
+
+
+def log_py_rows(ff, y):
+    """The rows of obj_fun_bern's log p(y|f) (laplace_approx_obj_funs.R:209-210, 249-251)."""
+    return y * plogis_log(ff) + (1 - y) * plogis_log(-np.asarray(ff, dtype=np.float64))
+
+
+def grad_loglik_fn_bern(ff, y, mu, Sigma12, Sigma22, Z):
+    """derivative_functions_of_data_likelihoods.R:188-235."""
+    d1 = dlog_py_dff_bern(ff, y)                                          # l.212
+    R = O.r_chol(Sigma22 + Sigma12.T @ ((1 / Z)[:, None] * Sigma12))      # l.215
+    d2 = -1 / Z * (ff - mu) + ((1 / Z)[:, None] * Sigma12) @ O.r_solve(
+        R, O.r_solve(R.T, Sigma12.T @ (1 / Z * (ff - mu))))               # l.220-221
+    return d1 + d2
+
+
+def obj_fun_bern(ff, mu, Z, Sigma12, Sigma22, y):
+    """laplace_approx_obj_funs.R:189-341 (log q(y | theta, xu, f_hat))."""
+    ff = np.asarray(ff, dtype=np.float64)
+    W = d2log_py_dff_bern(ff, y)                                          # l.225-226
+    Z2 = 1 + np.sqrt(-W) * Z * np.sqrt(-W)                                # l.246
+    log_py = np.sum(log_py_rows(ff, y))                                   # l.249-251
+    ZSig12 = (1 / Z)[:, None] * Sigma12
+    R = O.r_chol(Sigma22 + Sigma12.T @ ZSig12)                            # l.257
+    sw = np.sqrt(-W)[:, None] * Sigma12
+    R2 = O.r_chol(Sigma22 + sw.T @ ((1 / Z2)[:, None] * sw))              # l.261
+    logdetR2 = 2 * np.sum(np.log(np.diag(R2)))
+    R_Sigma22 = O.r_chol(Sigma22)                                         # l.265
+    v = O.r_solve(R.T, ZSig12.T @ (ff - mu))
+    quad = -0.5 * ((ff - mu) @ ((1 / Z) * (ff - mu))) + 0.5 * (v @ v)     # l.281-282
+    det_part_1 = -0.5 * (-2 * np.sum(np.log(np.diag(R_Sigma22))) + logdetR2)   # l.295-298
+    det_part_2 = -0.5 * np.sum(np.log(Z2))                                # l.299
+    return float(quad + log_py + det_part_1 + det_part_2)
+
+
+def newtrap_sparseGP_update(ff, W, Z, Sigma12, Sigma22, grad_psi, y, mu):
+    """newtrap_sparseGP.R:234-325 with dlog_py_dff = dlog_py_dff_bern."""
+    ZSig12 = (1 / Z)[:, None] * Sigma12
+    R = O.r_chol(Sigma22 + Sigma12.T @ ZSig12)
+    R3 = O.r_chol(Sigma22 + Sigma12.T @ (((Z - 1 / W) ** (-1))[:, None] * Sigma12))
+    omzw = 1 - Z * W
+    A11 = (Z / omzw) * dlog_py_dff_bern(ff, y)
+    A12 = omzw ** (-1) * (ff - mu)
+    A13 = O.r_solve(R.T, ((1 / omzw)[:, None] * Sigma12).T).T @ O.r_solve(R.T, ZSig12.T @ (ff - mu))
+    A2 = O.r_solve(R3.T, ((omzw ** (-1))[:, None] * Sigma12).T).T @ \
+        O.r_solve(R3.T, Sigma12.T @ ((1 / omzw) * grad_psi))
+    return ff + (A11 - A12 + A13 + A2)
+
+
+def newtrap_sparseGP(start_vals, cov_par, cov_fun, xy, xu, y, mu, delta=1e-6, maxit=1000,
+                     tol=1e-6, muu=None, trace=False):
+    """newtrap_sparseGP.R:6-186 for family = "bernoulli".  trace=True adds "stop_trace": per
+    loop test, (|obj_k - obj_{k-1}|, max |grad psi|), the two quantities of the stop rule
+    (l.100) -- the tests use it to keep their inputs away from the rule's threshold."""
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    mu = np.asarray(mu, dtype=np.float64).reshape(-1)
+    Sigma12, Sigma22, Z = O.laplace_mats(cov_par, cov_fun, xu, xy, delta)
+    ff = np.asarray(start_vals, dtype=np.float64).copy()
+    obj = [obj_fun_bern(ff, mu, Z, Sigma12, Sigma22, y)]
+    it = 1
+    it += 1
+    W = d2log_py_dff_bern(ff, y)
+    grad_psi = grad_loglik_fn_bern(ff, y, mu, Sigma12, Sigma22, Z)
+    ff = newtrap_sparseGP_update(ff, W, Z, Sigma12, Sigma22, grad_psi, y, mu)
+    obj.append(obj_fun_bern(ff, mu, Z, Sigma12, Sigma22, y))
+    stops = [(abs(obj[it - 1] - obj[it - 2]), float(np.max(np.abs(grad_psi))))]
+    while it < maxit and (abs(obj[it - 1] - obj[it - 2]) > tol or np.any(np.abs(grad_psi) > tol)):
+        it += 1
+        W = d2log_py_dff_bern(ff, y)
+        grad_psi = grad_loglik_fn_bern(ff, y, mu, Sigma12, Sigma22, Z)
+        ff = newtrap_sparseGP_update(ff, W, Z, Sigma12, Sigma22, grad_psi, y, mu)
+        obj.append(obj_fun_bern(ff, mu, Z, Sigma12, Sigma22, y))
+        stops.append((abs(obj[it - 1] - obj[it - 2]), float(np.max(np.abs(grad_psi)))))
+    out = {"gp": ff, "objective_function_values": np.array(obj), "gradient": grad_psi, "W": W}
+    if trace:
+        out["stop_trace"] = np.array(stops)
+    if muu is not None:
+        out["u_posterior_mean"], out["u_posterior_variance"] = O.laplace_posterior_u(
+            cov_par, cov_fun, xu, xy, y, mu, muu, ff, W, delta)
+    return out
+
+
+def stop_margins(stop_trace, tol):
+    """Relative distance |q - tol| / tol of the stop rule's deciding quantity q from tol, at the
+    stopping test and at the one before.  The rule continues while either quantity exceeds
+    tol, so q is the larger of the two."""
+    q = np.max(np.asarray(stop_trace), axis=1)
+    return abs(q[-1] - tol) / tol, (abs(q[-2] - tol) / tol if q.size > 1 else math.inf)
+
+
+def dlogq_dcov_par(cov_par, cov_fun, xu, xy, y, ff, mu, delta=1e-6):
+    """laplace_approx_gradient.R:25-336 with the Bernoulli d1, d2, d3 (knots fixed)."""
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    mu = np.asarray(mu, dtype=np.float64).reshape(-1)
+    ff = np.asarray(ff, dtype=np.float64).reshape(-1)
+    xy = O._as_matrix(xy)
+    xu = O._as_matrix(xu)
+    lnames = O.lnames_for(cov_fun, xy.shape[1])
+    Sigma12, Sigma22 = O._cov_mats(cov_par, cov_fun, xu, xy, delta, lnames)   # l.92-120
+    FF = O.r_solve(Sigma22, Sigma12.T)
+    Z = float(cov_par["sigma"]) ** 2 + float(cov_par["tau"]) ** 2 + delta - np.sum(Sigma12 * FF.T, axis=1)
+    W = d2log_py_dff_bern(ff, y)
+    B = 1 / (Z - (1 / W))                                                 # l.133
+    R = O.r_chol(Sigma22 + Sigma12.T @ ((1 / Z)[:, None] * Sigma12))
+    W3 = d3log_py_dff_bern(ff, y)
+    C = O.r_solve(Sigma22 + Sigma12.T @ (B[:, None] * Sigma12))
+    ZS = (1 / Z)[:, None] * Sigma12
+    comp2_1 = (1 / Z) * (ff - mu) - O.r_solve(R, O.r_solve(R.T, ZS.T)).T @ (ZS.T @ (ff - mu))
+    grad_log_py_ff = dlog_py_dff_bern(ff, y)
+    GG = O.r_solve(Sigma22, Sigma12.T @ grad_log_py_ff)                   # l.155
+    D = W - 1 / Z                                                         # l.161
+    E2 = np.eye(Sigma22.shape[0]) + O.r_solve(R.T, ZS.T) @ \
+        O.r_solve(R.T, (((1 / D) * (1 / Z))[:, None] * Sigma12).T).T      # l.164
+    RE = O.r_chol(E2) @ R
+    REinv = O.r_solve(RE)
+    coef = (1 / Z) * (1 / D)
+    tm = REinv.T @ (coef[None, :] * Sigma12.T)                            # l.171-177
+    comp4 = -(1 / D) + np.sum(tm * tm, axis=0)
+    grad = OrderedDict()
+    n = xy.shape[0]
+    for par_name in cov_par.keys():
+        dS12, dS22 = O._dmats(cov_par, cov_fun, xu, xy, par_name, lnames)
+        a1 = O.a1_diag(cov_fun, par_name, cov_par, lnames)
+        A1 = np.zeros(n) if a1 is None else np.full(n, a1)
+        A = A1 - np.sum((2 * dS12 - FF.T @ dS22) * FF.T, axis=1)
+        comp1, comp2 = O._gaussian_comps(A, B, C, FF, Sigma12, Sigma22, dS12, dS22, comp2_1)
+        comp3_1 = A * grad_log_py_ff + 2 * dS12 @ GG - FF.T @ dS22 @ GG   # l.308-310
+        BS12 = B[:, None] * Sigma12
+        comp3 = -(1 / W) * (B * comp3_1) + (1 / W) * (BS12 @ (C @ (Sigma12.T @ (B * comp3_1))))  # l.313-314
+        grad[par_name] = float(0.5 * comp2 - 0.5 * comp1 - 0.5 * ((comp4 * (-W3)) @ comp3))      # l.334-336
+    return {"gradient": grad}
+
+
+def laplace_grad_ascent(cov_par_start, cov_fun, xu, xy, y, ff, mu, muu, opt=None):
+    """laplace_gradient_ascent.R:10-623 for family = "bernoulli" (theta only): oracle.drivers'
+    generic ascent loop around this module's NR and gradient."""
+    from oracle import drivers as D
+    o = D._opts(opt, {"maxit_nr": 1000, "tol_nr": 1e-6})
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    mu = np.asarray(mu, dtype=np.float64).reshape(-1)
+    muu = np.asarray(muu, dtype=np.float64).reshape(-1)
+    dl = o["delta"]
+    state = {"f": np.asarray(ff, dtype=np.float64).copy()}
+
+    def evaluate(cp, U):
+        nr = newtrap_sparseGP(state["f"], cp, cov_fun, xy, U, y, mu, dl, o["maxit_nr"],
+                              o["tol_nr"], muu=muu)
+        state["f"] = nr["gp"]
+        ov = nr["objective_function_values"]
+        g = dlogq_dcov_par(cp, cov_fun, U, xy, y, nr["gp"], mu, dl)["gradient"]
+        return ov[-1], g, None, len(ov), nr["u_posterior_mean"], nr["u_posterior_variance"]
+
+    out = D._ascent(evaluate, lambda cp, U, last: (last[1], last[2]), cov_par_start, xu, xy, True,
+                    False, o)
+    out.update({"fmax": state["f"], "nr_iter": np.array([e[0] for e in out["extras"]])})
+    return out
+
+
+# --------------------------------------------------------------------------------------
+# Test inputs shared by tests/test_bernoulli_oracle.py and tests/test_gpu_bernoulli.py
+# --------------------------------------------------------------------------------------
+TOL_NR = 1e-5
+
+# name -> (n, m, d, cov_fun, cov_par or None for the vignette's, coincident knots, seed)
+CASES = OrderedDict([
+    ("sqexp_300_20", (300, 20, 2, "sqexp", (1.0, 2.0, 0.1), False, 11)),
+    ("ard_350_25", (350, 25, 3, "ard", (2.0, 1.5, 1.8, 2.1, 0.2), True, 12)),
+    ("sqexp_257_1", (257, 1, 2, "sqexp", (1.0, 2.0, 0.1), False, 11)),
+    ("sqexp_900_130", (900, 130, 2, "sqexp", (1.0, 2.0, 0.1), False, 11)),
+    ("vignette_200_5", (200, 5, 2, "sqexp", None, False, 13)),
+])
+
+
+def problem(name):
+    """make_bernoulli_problem for a CASES entry (knots 0, 1 moved onto data rows 3, n - 1 when
+    the case asks for coincident knots)."""
+    from sparsergps_amd.workloads import make_bernoulli_problem
+    n, m, d, cov_fun, th, coinc, seed = CASES[name]
+    cp = None
+    if th is not None:
+        names = ["sigma"] + ([f"l{c + 1}" for c in range(d)] if cov_fun == "ard" else ["l"]) + ["tau"]
+        cp = OrderedDict(zip(names, th))
+    P = make_bernoulli_problem(n, m, d=d, seed=seed, cov_par=cp)
+    P["cov_fun"] = cov_fun
+    if coinc:
+        P["U"][:2] = P["X"][[3, n - 1]]
+    return P
+
+
+FIXTURE = "bernoulli_small.npz"
+FIXTURE_CASE = "sqexp_300_20"
+
+
+def fixture_record():
+    """What tests/golden/bernoulli_small.npz holds: the inputs of FIXTURE_CASE and, from this
+    restatement, the NR objective values, the mode and the gradient there."""
+    P = problem(FIXTURE_CASE)
+    nr = newtrap_sparseGP(P["f0"], P["cov_par"], P["cov_fun"], P["X"], P["U"], P["y"], P["mu"],
+                          P["delta"], tol=TOL_NR)
+    g = dlogq_dcov_par(P["cov_par"], P["cov_fun"], P["U"], P["X"], P["y"], nr["gp"], P["mu"],
+                       P["delta"])["gradient"]
+    return dict(X=P["X"], U=P["U"], y=P["y"], mu=P["mu"], f0=P["f0"],
+                theta=np.array(list(P["cov_par"].values())), delta=np.array(P["delta"]),
+                tol=np.array(TOL_NR), mode=nr["gp"],
+                objective_function_values=nr["objective_function_values"],
+                gradient=np.array([g[k] for k in P["cov_par"]]))
+
+
+if __name__ == "__main__":      # python tests/bern_oracle.py: rewrite the fixture
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    np.savez_compressed(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", FIXTURE),
+                        **fixture_record())
