@@ -295,7 +295,8 @@ struct sgp_ctx {
   hipStream_t aux_lo = nullptr;           // ... at normal priority (the Bm chain keeps its CUs)
   double* slab_aux = nullptr;             // partials of the aux stream's small reductions
   double* rr_dev = nullptr;               // r^T r of the resident r (set with r)
-  double* mmpart = nullptr;               // VI's m-vector row terms (mp), read on aux_lo
+  double* mmpart = nullptr;               // VI's m-vector row terms (mp), read on aux_lo;
+                                          // then the folded adjoint's column terms (2 mp)
   unsigned* rsync = nullptr;              // the SYRK reduction's slice tickets (kept zeroed)
   // launch-bound Bm factorisation captured once per (mp, S pointer) and replayed
   // Poisson-Laplace state (row/knot vectors allocated on first use)
@@ -327,8 +328,13 @@ struct sgp_ctx {
 namespace {
 
 constexpr int SC_LD22 = 0, SC_LDB = 1, SC_TU = 2, SC_TRKS = 3, SC_TRBS = 4, SC_RR = 5,
-              SC_G22 = 16;  // SC_G22 .. SC_G22 + P - 1 (contract_kmm records)
-constexpr int SC_N = 64;
+              // VI's folded adjoint (launch_vi_fold_cols): sum_j c_j, alpha^T alpha, and
+              // SC_EL .. SC_EL + L - 1 = sum_j u~_jc^2 c_j
+              SC_ESIG = 6, SC_ATA = 7,
+              SC_G22 = 16,  // SC_G22 .. SC_G22 + P - 1 (contract_kmm records)
+              SC_EL = 64;
+constexpr int SC_N = 96;
+static_assert(SC_G22 + SGP_MAXD + 2 <= SC_EL && SC_EL + SGP_MAXD <= SC_N, "sc slots overlap");
 // per-block partials of the small reductions: k_contract_kmm writes up to 1024 blocks x (P-1)
 // records (P <= SGP_MAXD + 2), the dot/colsum helpers at most 1024 x 1
 constexpr int SLAB_SMALL = 1024 * (SGP_MAXD + 2);
@@ -916,7 +922,7 @@ int sgp_ctx_create(sgp_ctx** out, int device, const double* X, int64_t n, int64_
   st = st ? st : dalloc(&c->slab_small, c->slab_small_cap);
   st = st ? st : dalloc(&c->slab_aux, c->slab_small_cap);
   st = st ? st : dalloc(&c->rr_dev, 1);
-  st = st ? st : dalloc(&c->mmpart, mp);
+  st = st ? st : dalloc(&c->mmpart, 3 * mp);
   st = st ? st : dalloc(&c->sc, SC_N);
   st = st ? st : dalloc(&c->y, np_);
   st = st ? st : dalloc(&c->mu, np_);
@@ -1172,8 +1178,10 @@ static int contract_pass(sgp_ctx* c, const double* M, ConArgs ca, double* rec_ou
                          double* knot_out, bool knot_acc) {
   int64_t nrec = 0, nwg = 0;
   if (c->knot_on) ca.knot_slab = c->knot_slab;
-  const bool fused = ca.uvec != nullptr && ca.alpha_in == nullptr;
+  const bool fused = ca.uvec != nullptr && ca.alpha_in == nullptr && !ca.vi_fold;
   if (fused) ca.alpha_out = c->alpha;   // k_coinc needs the fused alpha_i
+  // (VI's folded adjoint: the coincidence scan reads the same pair as the contraction, r / z
+  // and P', launch_records)
   // the balanced launch where the tile grid leaves a mostly idle last round (opt-in, see
   // con_sk_enabled)
   if (c->sk_ws) {
@@ -1192,7 +1200,8 @@ static int contract_pass(sgp_ctx* c, const double* M, ConArgs ca, double* rec_ou
   // hashing once per knot set (cflag written), later evaluations only revisit the flagged rows
   const bool flags_known = c->cflag_gen == c->knots_gen;
   HIPCHK(launch_records(c->slab_con, nrec, nwg, c->X, c->n_pad, c->n, c->kp.d, c->U, c->mp, c->m,
-                        c->khash, c->kidx, c->K, c->mp, M, ca, fused ? c->alpha : ca.alpha_in,
+                        c->khash, c->kidx, c->K, c->mp, M, ca,
+                        ca.vi_fold ? ca.r : (fused ? c->alpha : ca.alpha_in),
                         c->slab_small, c->slab_small_cap, 1 + c->kp.L, rec_out, c->cflag,
                         flags_known ? 2 : 1, c->stream, c->defer_rec ? &c->rec_defer : nullptr));
   c->cflag_gen = c->knots_gen;
@@ -1543,12 +1552,15 @@ int sgp_vi_phase2(sgp_ctx* c, const double* red1, int64_t n_global, unsigned fla
       c->phase = 2;
       return SGP_OK;
     }
-    // u = Binv t / z, P = tau^-2 K22inv - z^-1 Binv and tr(Binv S)'s row terms in one launch
-    // between the Bm chain and the contraction (the critical path); t.u, tr(Binv S) and r^T r
-    // on aux_lo below (only the finish reads them)
+    // u = Binv t / z, then P' = tau^-2 K22inv - z^-1 Binv - z^-1 u u^T and tr(Binv S)'s row
+    // terms, between the Bm chain and the contraction (the critical path).  The rank-1 term
+    // makes K P' = K P - (K u) u^T / z, so the contraction's adjoint G = (r/z) u^T + K P' needs
+    // no K u.  Two launches: every row of P' needs all of u, and u all of Binv.  t.u,
+    // tr(Binv S) and r^T r on aux_lo below (only the finish reads them)
+    HIPCHK(dense_gemv(c->Binv, mp, t, 1.0 / z, c->uvec, c->stream));
     if (!k22_via_t) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_k22, 0));
-    HIPCHK(launch_vi_mm_rows(c->Binv, c->K22inv, S, t, mp, 1.0 / z, 1.0 / kp.tau2, -1.0 / z,
-                             c->uvec, c->Pm, c->mmpart, c->stream));
+    HIPCHK(launch_vi_mm_rows(c->Binv, c->K22inv, S, c->uvec, mp, 1.0 / kp.tau2, -1.0 / z,
+                             -1.0 / z, c->Pm, c->mmpart, c->stream));
     HIPCHK(hipEventRecord(c->ev_bm, c->stream));
   }
   {
@@ -1564,8 +1576,8 @@ int sgp_vi_phase2(sgp_ctx* c, const double* red1, int64_t n_global, unsigned fla
                                -0.5, 0.5, -1.0 / (2.0 * kp.tau2), nullptr, nullptr, 0.0,
                                c->slab_aux, c->slab_small_cap, &nb, c->aux_lo));
     HIPCHK(launch_colsum(c->slab_aux, nb, kp.P, c->sc + SC_G22, c->aux_lo));
-    HIPCHK(hipEventRecord(c->ev_m3, c->aux_lo));
   }
+  int st2 = SGP_OK;
   {
     Scope tm(c, "contract_knm");
     ConArgs ca;
@@ -1573,11 +1585,20 @@ int sgp_vi_phase2(sgp_ctx* c, const double* red1, int64_t n_global, unsigned fla
     ca.invz = 1.0 / z;
     ca.uvec = c->uvec;
     ca.cdiag = c->cdiag;
-    ca.count_a2 = 1;
-    int st2 = contract_pass(c, c->Pm, ca, red2, red2 + sgp_vi_red2_count(kp.kernel, kp.d), false);
-    if (st2) return st2;
+    ca.vi_fold = true;   // G = (r/z) u^T + K P': no K u fold, no column sums, no alpha^T alpha
+    st2 = contract_pass(c, c->Pm, ca, red2, red2 + sgp_vi_red2_count(kp.kernel, kp.d), false);
   }
-  HIPCHK(hipStreamWaitEvent(c->stream, c->ev_m3, 0));   // G22 records (aux_lo)
+  // the terms the folded contraction leaves out (its column sums c_j and alpha^T alpha), from
+  // the reduced S, t and r^T r: with several ranks they enter once, like tr(Binv S).  On aux_lo
+  // behind the G22 records, issued after the contraction so that the host reaches the
+  // contraction's launch no later than before
+  if (!st2)
+    HIPCHK(launch_vi_fold_cols(kp, S, c->Pm, t, c->uvec, c->U, c->mp, c->m, mp, 1.0 / z,
+                               red1 + toff + mp, c->mmpart + mp, !c->knot_on, c->sc + SC_ESIG,
+                               c->sc + SC_EL, c->sc + SC_ATA, c->aux_lo));
+  HIPCHK(hipEventRecord(c->ev_m3, c->aux_lo));
+  if (st2) return st2;
+  HIPCHK(hipStreamWaitEvent(c->stream, c->ev_m3, 0));   // G22 records, folded terms (aux_lo)
   c->phase = 2;
   return SGP_OK;
 }
@@ -1642,13 +1663,17 @@ int sgp_vi_finish(sgp_ctx* c, const double* red2, double* obj, double* grad) {
     return SGP_OK;
   }
   // delbo_dcov_par (vi_functions.R:259-419) in adjoint form
-  // red2 = [e_sig, e_l(L), c_sum, c_cnt, c_dg, alpha^T alpha]
-  const double e_sig = r2[0];
-  const double c_sum = r2[1 + L], c_cnt = r2[2 + L], c_dg = r2[3 + L], aTa = r2[4 + L];
+  // red2 = [e_sig, e_l(L), c_sum, c_cnt, c_dg, alpha^T alpha]: alpha^T alpha is zero from the
+  // folded contraction and, with knots fixed, so is e_sig, and e_l lacks sum_j u~_jc^2 c_j;
+  // those terms are replicated scalars (sc) of the reduced S, t and r^T r, added here once
+  // (zero where the contraction formed them itself)
+  const double e_sig = r2[0] + sc[SC_ESIG];
+  const double c_sum = r2[1 + L], c_cnt = r2[2 + L], c_dg = r2[3 + L];
+  const double aTa = r2[4 + L] + sc[SC_ATA];
   const double trSinv = n / z - trBS / (z * z);
   const double trW = 0.5 * (aTa - trSinv);
   grad[0] = 2.0 * e_sig + sc[SC_G22] - n * kp.sig2 / kp.tau2;
-  for (int q = 0; q < L; ++q) grad[1 + q] = r2[1 + q] + sc[SC_G22 + 1 + q];
+  for (int q = 0; q < L; ++q) grad[1 + q] = r2[1 + q] + sc[SC_EL + q] + sc[SC_G22 + 1 + q];
   grad[L + 1] = 2.0 * kp.tau2 * (c_sum - (c_cnt - c->delta * c_dg) / kp.tau2) +
                 2.0 * kp.tau2 * trW - 2.0 * trace_term;
   return knot_finish(c, red2 + n2, c->uvec, c->K22inv, c->Binv, c->M3, -0.5, 0.5,

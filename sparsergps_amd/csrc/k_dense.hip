@@ -908,34 +908,109 @@ __global__ void __launch_bounds__(256) k_fitc_omega(const double* __restrict__ a
   if (threadIdx.x == 0) slab[blockIdx.x] = s;
 }
 
-// VI phase-2 row pass over the m x m operands, one wave per row j (replaces a GEMV, an axpby
-// and a dot-product pair):  u_j = invz (Binv t)_j,  P_j: = a K22inv_j: + b Binv_j:,
-// part_j = sum_k Binv_jk S_jk.  The GEMV keeps k_gemv's lane-strided summation order.
+// VI phase-2 row pass over the m x m operands, one wave per row j (replaces an axpby, a rank-1
+// update and a dot-product pair); u = invz Binv t is given (k_gemv before it: every row needs
+// all of u):  P'_j: = a K22inv_j: + b Binv_j: + c1 u_j u^T,  part_j = sum_k Binv_jk S_jk.
+// With c1 = -1/z, K P' = K P - (K u) u^T / z: the contraction's adjoint
+// G = (r/z) u^T + K P' needs no K u.
 __global__ void __launch_bounds__(256) k_vi_mm_rows(const double* __restrict__ Binv,
-                                                    const double* __restrict__ K22inv,
-                                                    const double* __restrict__ S,
-                                                    const double* __restrict__ t, int64_t mp,
-                                                    double invz, double a, double b,
-                                                    double* __restrict__ u,
-                                                    double* __restrict__ P,
-                                                    double* __restrict__ part) {
+                                                         const double* __restrict__ K22inv,
+                                                         const double* __restrict__ S,
+                                                         const double* __restrict__ u, int64_t mp,
+                                                         double a, double b, double c1,
+                                                         double* __restrict__ P,
+                                                         double* __restrict__ part) {
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= mp) return;
   const int64_t o = row * mp;
-  double su = 0.0, sp = 0.0;
+  const double cu = c1 * u[row];
+  double sp = 0.0;
   for (int64_t j = lane; j < mp; j += 64) {
     const double bv = Binv[o + j];
-    su = fma(bv, t[j], su);
     sp = fma(bv, S[o + j], sp);
-    P[o + j] = a * K22inv[o + j] + b * bv;
+    P[o + j] = fma(cu, u[j], a * K22inv[o + j] + b * bv);
   }
-  su = wave_sum(su);
   sp = wave_sum(sp);
-  if (lane == 0) {
-    u[row] = invz * su;
-    part[row] = sp;
+  if (lane == 0) part[row] = sp;
+}
+
+// Column pass of VI's folded adjoint, 64 columns x 4 row strips per block:
+//   cs[j] = sum_k S_kj P'_kj,  cs[mp + j] = (S u)_j = sum_k S_kj u_k   (S is symmetric)
+__global__ void __launch_bounds__(256) k_vi_fold_cols(const double* __restrict__ S,
+                                                      const double* __restrict__ P,
+                                                      const double* __restrict__ u, int64_t mp,
+                                                      double* __restrict__ cs) {
+  __shared__ double sh[2][4][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int64_t j = (int64_t)blockIdx.x * 64 + tx;
+  double sp = 0.0, su = 0.0;
+  if (j < mp) {
+    for (int64_t k = ty; k < mp; k += 4) {
+      const double sv = S[k * mp + j];
+      sp = fma(sv, P[k * mp + j], sp);
+      su = fma(sv, u[k], su);
+    }
   }
+  sh[0][ty][tx] = sp;
+  sh[1][ty][tx] = su;
+  __syncthreads();
+  if (ty == 0 && j < mp) {
+    cs[j] = (sh[0][0][tx] + sh[0][1][tx]) + (sh[0][2][tx] + sh[0][3][tx]);
+    cs[mp + j] = (sh[1][0][tx] + sh[1][1][tx]) + (sh[1][2][tx] + sh[1][3][tx]);
+  }
+}
+
+// The folded adjoint's replicated terms from the column pass (one block, fixed order):
+//   c_j = u_j t_j invz + cs[j];  *esig_out = sum_j c_j;  el_out[c] = sum_j u~_jc^2 c_j (ARD) or
+//   el_out[0] = rl2[0] sum_jc u_jc^2 c_j (esig_out, el_out: only with col_terms);
+//   *ata_out = (rr - 2 u.t + u.(S u)) invz^2
+__global__ void __launch_bounds__(256) k_vi_fold_scalars(KernParams kp, const double* __restrict__ cs,
+                                                         const double* __restrict__ t,
+                                                         const double* __restrict__ u,
+                                                         const double* __restrict__ U, int64_t ldu,
+                                                         int64_t m, int64_t mp, double invz,
+                                                         const double* __restrict__ rr,
+                                                         int col_terms,
+                                                         double* __restrict__ esig_out,
+                                                         double* __restrict__ el_out,
+                                                         double* __restrict__ ata_out) {
+  __shared__ double sh[4];
+  const bool ard = kp.kernel == 1;
+  const int d = kp.d;
+  double e = 0.0, tu = 0.0, usu = 0.0, esq = 0.0;
+  for (int64_t j = threadIdx.x; j < m; j += 256) {
+    const double c = fma(u[j] * invz, t[j], cs[j]);
+    e += c;
+    tu = fma(u[j], t[j], tu);
+    usu = fma(u[j], cs[mp + j], usu);
+    if (!ard && col_terms)
+      for (int q = 0; q < d; ++q) {
+        const double uv = U[j + q * ldu];
+        esq = fma(uv * uv, c, esq);
+      }
+  }
+  e = block_sum(e, sh);
+  tu = block_sum(tu, sh);
+  usu = block_sum(usu, sh);
+  if (threadIdx.x == 0) *ata_out = (*rr - 2.0 * tu + usu) * invz * invz;
+  if (!col_terms) return;   // uniform
+  if (ard) {
+    // one coordinate at a time: the block sums keep a fixed order
+    for (int q = 0; q < d; ++q) {
+      double v = 0.0;
+      for (int64_t j = threadIdx.x; j < m; j += 256) {
+        const double uv = U[j + q * ldu] * kp.rl[q];
+        v = fma(uv * uv, fma(u[j] * invz, t[j], cs[j]), v);
+      }
+      v = block_sum(v, sh);
+      if (threadIdx.x == 0) el_out[q] = v;
+    }
+  } else {
+    esq = block_sum(esq, sh);
+    if (threadIdx.x == 0) el_out[0] = esq * kp.rl2[0];
+  }
+  if (threadIdx.x == 0) *esig_out = e;
 }
 
 // sc[0] = t . u, sc[1] = sum part (= tr(Binv S)), sc[2] = *rr; one block, fixed order
@@ -964,10 +1039,22 @@ __global__ void __launch_bounds__(256) k_vi_mm_scalars(const double* __restrict_
 }  // namespace
 
 hipError_t launch_vi_mm_rows(const double* Binv, const double* K22inv, const double* S,
-                             const double* t, int64_t mp, double invz, double a, double b,
-                             double* u, double* P, double* part, hipStream_t s) {
-  hipLaunchKernelGGL(k_vi_mm_rows, dim3((unsigned)((mp + 3) / 4)), dim3(256), 0, s, Binv, K22inv,
-                     S, t, mp, invz, a, b, u, P, part);
+                                  const double* u, int64_t mp, double a, double b, double c1,
+                                  double* P, double* part, hipStream_t s) {
+  hipLaunchKernelGGL(k_vi_mm_rows, dim3((unsigned)((mp + 3) / 4)), dim3(256), 0, s, Binv,
+                     K22inv, S, u, mp, a, b, c1, P, part);
+  return hipGetLastError();
+}
+
+hipError_t launch_vi_fold_cols(const KernParams& kp, const double* S, const double* P,
+                               const double* t, const double* u, const double* U, int64_t ldu,
+                               int64_t m, int64_t mp, double invz, const double* rr, double* cs,
+                               bool col_terms, double* esig_out, double* el_out,
+                               double* ata_out, hipStream_t s) {
+  hipLaunchKernelGGL(k_vi_fold_cols, dim3((unsigned)((mp + 63) / 64)), dim3(256), 0, s, S, P, u,
+                     mp, cs);
+  hipLaunchKernelGGL(k_vi_fold_scalars, dim3(1), dim3(256), 0, s, kp, cs, t, u, U, ldu, m, mp,
+                     invz, rr, col_terms ? 1 : 0, esig_out, el_out, ata_out);
   return hipGetLastError();
 }
 

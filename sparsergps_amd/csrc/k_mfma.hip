@@ -952,6 +952,11 @@ enum { EPI_GRAD = 0, EPI_ROWQUAD = 1 };
 
 // KU (row quadratic forms without u: the Z pass): false compiles the K u fold out of the k-loop
 // T2 (FROM_T only): a second stored product folded in (ConArgs::tin2)
+// VIF (EPI_GRAD, with KU = false): VI's folded adjoint G = (r/z) u^T + K P' (ConArgs::vi_fold).
+//   The row factor is r_i * invz and the record's alpha^T alpha field is zero.  Without KNOT the
+//   epilogue forms no column sums C_j either: e_sig is zero and e_l[c] = sum_j D[j][8+c] -
+//   2 u~_jc D[j][c].  With KNOT the column sums stay: the knot partials D[j][c] - u~_jc C_j
+//   cancel per tile, where the terms are small, not after the reduction over all rows
 constexpr int CON_A_SZ = T128 * SA;   // 2176 (keeps the B image 16-byte aligned)
 constexpr int CON_B_SZ = BK * SB;     // 2304
 constexpr int CON_LDS = 2 * (CON_A_SZ + CON_B_SZ);
@@ -979,7 +984,8 @@ __device__ __forceinline__ unsigned con_ldu_sc1(const unsigned* p) {
 // the k-loop), CON_HEAD (`part` chooses at run time between CON_HEAD and CON_FULL).  The tail and
 // the head never share one copy of the body: compiled together the accumulators spilled
 // ~250 VGPRs
-template <int DT, int EPI, bool V2, bool KNOT, bool FROM_T, bool KU, bool T2, int SKM>
+template <int DT, int EPI, bool V2, bool KNOT, bool FROM_T, bool KU, bool T2, int SKM,
+          bool VIF = false>
 __device__ __forceinline__ void con_tile(
     const KernParams& kp, const double* __restrict__ K, const double* __restrict__ M,
     const double* __restrict__ X, int64_t ldx, int64_t n, int64_t n_pad,
@@ -999,6 +1005,7 @@ __device__ __forceinline__ void con_tile(
   const int wr = wv >> 1, wc = wv & 1;
   const bool with_u = KU && (uvec != nullptr) && (ca.alpha_in == nullptr);   // fuse K u into the loop
   constexpr bool with_v = V2;   // second rank-1 term (Laplace), compiled in only where used
+  constexpr bool NOCS = VIF && !KNOT;   // no column sums in the epilogue
 
   d4 acc[4][4];
 #pragma unroll
@@ -1171,9 +1178,15 @@ __device__ __forceinline__ void con_tile(
   double a2 = 0.0;                                    // alpha^2, counted once (tj == 0)
   if ((tid & 1) == 0) {
     const int64_t i = i0 + arow;
-    const double iz = ca.invz_vec ? ca.invz_vec[i] : ca.invz;
-    const double al = ca.alpha_in ? ca.alpha_in[i]
-                                  : (with_u ? (r[i] - ku) * iz : 0.0);   // padded rows -> 0
+    double iz, al;
+    if constexpr (VIF) {
+      iz = ca.invz;
+      al = r[i] * iz;
+    } else {
+      iz = ca.invz_vec ? ca.invz_vec[i] : ca.invz;
+      al = ca.alpha_in ? ca.alpha_in[i]
+                       : (with_u ? (r[i] - ku) * iz : 0.0);   // padded rows -> 0
+    }
     // rows past n: every row factor 0, so G = 0 there and the epilogue needs no validity mask
     // (K12 is exactly 0 in the padded columns j >= m, and T = K M is finite: W = G o K = 0)
     const bool iv = i < n;
@@ -1181,9 +1194,11 @@ __device__ __forceinline__ void con_tile(
     s_rs[arow] = iv ? (ca.rs_vec ? ca.rs * ca.rs_vec[i] : ca.rs) : 0.0;
     if constexpr (T2) s_rs2[arow] = iv ? (ca.rs_vec2 ? ca.rs2 * ca.rs_vec2[i] : ca.rs2) : 0.0;
     s_beta[arow] = (with_v && iv) ? ca.beta_in[i] : 0.0;
-    if (tj == 0) {
-      if (ca.count_a2 && i < n) a2 = al * al;
-      if (ca.alpha_out) ca.alpha_out[i] = al;
+    if constexpr (!VIF) {
+      if (tj == 0) {
+        if (ca.count_a2 && i < n) a2 = al * al;
+        if (ca.alpha_out) ca.alpha_out[i] = al;
+      }
     }
   }
   const double* Kt = K + i0 * mp + j0;
@@ -1383,7 +1398,7 @@ __device__ __forceinline__ void con_tile(
               // keep the select (measured 5 % slower without it) and so does Laplace with knot
               // gradients (without it its 256 VGPRs spill)
               if constexpr ((V2 && KNOT) || FROM_T) w = (j0 + col < m && i0 + row < n) ? w : 0.0;
-              Cc[fn] += w;
+              if constexpr (!NOCS) Cc[fn] += w;
               acc[fm][fn][q] = w;
             }
           }
@@ -1433,6 +1448,16 @@ __device__ __forceinline__ void con_tile(
         double E = 0.0;
 #pragma unroll
         for (int fn = 0; fn < 4; ++fn) {
+          if constexpr (NOCS) {
+            // no column sums: the u~^2 C_j terms come from m x m operands
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int jl = wc * 64 + fn * 16 + (lane >> 4) + 4 * q;
+              const double u = cok ? s_us[jl * sus + cc] : 0.0;
+              const double pv = P[fn][q];
+              E += (cp >= 8) ? pv : -2.0 * (u * pv);
+            }
+          } else {
           double C = Cc[fn];
           C += __shfl_xor(C, 16, 64);
           C += __shfl_xor(C, 32, 64);            // every lane: C of column (lane & 15)
@@ -1447,6 +1472,7 @@ __device__ __forceinline__ void con_tile(
             if constexpr (KNOT) {
               if (cp < 8) s_kn[(wr * T128 + jl) * 8 + cc] = pv - u * Cq;
             }
+          }
           }
         }
         E += __shfl_xor(E, 8, 64);
@@ -1478,11 +1504,12 @@ __device__ __forceinline__ void con_tile(
     SGP_PROBE_CON_STAMP(6);
     // record = [e_sig, e_l[0..L-1], c_sum, c_cnt, c_dg, alpha^T alpha]
     // (the coincidence fields stay zero here; k_coinc adds them)
-    double v;
-    v = wave_sum(e_sig);
+    double v = 0.0;
+    if constexpr (!NOCS) v = wave_sum(e_sig);
     if (lane == 0) red[wv][0] = v;
     if (!ard && lane == 0) red[wv][1] = e_sq * rl2s;   // ARD: red[wv][1 + c] written above
-    v = wave_sum(a2);
+    v = 0.0;
+    if constexpr (!VIF) v = wave_sum(a2);
     if (lane == 0) {
       red[wv][1 + L] = 0.0;
       red[wv][2 + L] = 0.0;
@@ -1499,7 +1526,7 @@ __device__ __forceinline__ void con_tile(
 
 // one 128 x 128 output tile per workgroup (grid = tiles), XCD-aware tile order
 template <int DT, int EPI, bool V2 = false, bool KNOT = false, bool FROM_T = false, bool KU = true,
-          bool T2 = false>
+          bool T2 = false, bool VIF = false>
 __global__ void __launch_bounds__(256, 2)
 k_contract(KernParams kp, const double* __restrict__ K, const double* __restrict__ M,
            const double* __restrict__ X, int64_t ldx, int64_t n, int64_t n_pad,
@@ -1511,7 +1538,7 @@ k_contract(KernParams kp, const double* __restrict__ K, const double* __restrict
   const int64_t ntj = mp / T128;
   const int64_t nwg = (n_pad / T128) * ntj;
   const int64_t wgid = xcd_remap(blockIdx.x, nwg);
-  con_tile<DT, EPI, V2, KNOT, FROM_T, KU, T2, 0>(
+  con_tile<DT, EPI, V2, KNOT, FROM_T, KU, T2, 0, VIF>(
       kp, K, M, X, ldx, n, n_pad, U, ldu, m, mp, ca, slab, nrec, rowq, wgid / ntj, wgid % ntj,
       wgid, 0, (int)(mp / BK), lds, red, s_uk, ConSK{}, CON_FULL, (int)threadIdx.x);
 }
@@ -1527,7 +1554,8 @@ k_contract(KernParams kp, const double* __restrict__ K, const double* __restrict
 // range that starts inside a tile computes that tile's tail FIRST, before its whole rounds, and
 // hands it to workgroup v - 1, which holds the tile's head at the very end of its own work and
 // adds the tail before the tile's one epilogue.
-template <int DT, bool KNOT>
+// VIF: the folded adjoint (no K u fold; no column sums without KNOT), as k_contract's
+template <int DT, bool KNOT, bool VIF = false>
 __global__ void __launch_bounds__(256, 2)
 k_contract_sk(KernParams kp, const double* __restrict__ K, const double* __restrict__ M,
               const double* __restrict__ X, int64_t ldx, int64_t n, int64_t n_pad,
@@ -1551,7 +1579,7 @@ k_contract_sk(KernParams kp, const double* __restrict__ K, const double* __restr
     const int kb = (int)(u % S);
     ConSK p = sk;
     p.slot = v;
-    con_tile<DT, EPI_GRAD, false, KNOT, false, true, false, CON_TAIL>(
+    con_tile<DT, EPI_GRAD, false, KNOT, false, !VIF, false, CON_TAIL, VIF>(
         kp, K, M, X, ldx, n, n_pad, U, ldu, m, mp, ca, slab, nrec, nullptr, tile / ntj,
         tile % ntj, tile, kb, S, lds, red, s_uk, p, CON_TAIL, (int)threadIdx.x);
     u += S - kb;
@@ -1579,7 +1607,7 @@ k_contract_sk(KernParams kp, const double* __restrict__ K, const double* __restr
     // kept live across the k-loop
     int tid;
     asm volatile("v_mov_b32 %0, %1" : "=v"(tid) : "v"((int)threadIdx.x));
-    con_tile<DT, EPI_GRAD, false, KNOT, false, true, false, CON_HEAD>(
+    con_tile<DT, EPI_GRAD, false, KNOT, false, !VIF, false, CON_HEAD, VIF>(
         kp, K, M, X, ldx, n, n_pad, U, ldu, m, mp, ca, slab, nrec, nullptr, tile / ntj,
         tile % ntj, tile, 0, ke, lds, red, s_uk, p, ke < S ? CON_HEAD : CON_FULL, tid);
     __syncthreads();   // the next tile's operand staging reuses the epilogue's LDS
@@ -1662,6 +1690,7 @@ struct CoincArgs {
   const double* rs_vec; double rs; const double* cdiag;
   uint8_t* cflag; int flag_mode;
   const double* M2; const double* rs_vec2; double rs2;   // ConArgs::M2 (fused two-product pass)
+  double ascale;   // alpha_i = alpha[i] * ascale (1; VI's folded adjoint: alpha = r, ascale = 1/z)
 };
 
 __device__ __forceinline__ void coinc_body(const CoincArgs& ca, int64_t bid, int64_t nblk,
@@ -1705,7 +1734,7 @@ __device__ __forceinline__ void coinc_body(const CoincArgs& ca, int64_t bid, int
         g = fma(ca.rs_vec2 ? ca.rs2 * ca.rs_vec2[i] : ca.rs2, t2, g);
       }
       if (beta) g = fma(beta[i], vvec[j], g);
-      if (alpha && uvec) g = fma(alpha[i], uvec[j], g);
+      if (alpha && uvec) g = fma(alpha[i] * ca.ascale, uvec[j], g);
       a[0] += g;
       a[1] += 1.0;
       a[2] += cdiag ? cdiag[j] : 0.0;
@@ -2300,7 +2329,7 @@ hipError_t launch_records(const double* slab, int64_t nrow, int64_t len, const d
   double* part_c = part + nrow * G;
   CoincArgs ca{X, ldx, n, d, U, ldu, m, khash, kidx, K, mp, M, alpha, cg.uvec, cg.beta_in,
                cg.vvec, cg.rs_vec, cg.rs, cg.cdiag, cflag, flag_mode, cg.M2, cg.rs_vec2,
-               cg.rs2};
+               cg.rs2, cg.vi_fold ? cg.invz : 1.0};
   hipLaunchKernelGGL(k_rec_pass1, dim3((unsigned)(nbc + nrow * G)), dim3(256), 0, s, ca,
                      (int)nbc, slab, len, G, part_r, part_c);
   RecPass2 p2;
@@ -2360,11 +2389,19 @@ static void launch_con_grad(bool v2, const KernParams& kp, const double* K, cons
     sk.epoch = ca.sk_epoch;
     sk.status = ca.sk_status;
     sk.dp = ca.sk_dp;
+    if (ca.vi_fold)
+      hipLaunchKernelGGL((k_contract_sk<DT, KNOT, true>), dim3((unsigned)ca.sk_slots), dim3(256),
+                         0, s, kp, K, M, X, ldx, n, n_pad, U, ldu, m, mp, ca, slab, nrec, sk);
+    else
     hipLaunchKernelGGL((k_contract_sk<DT, KNOT>), dim3((unsigned)ca.sk_slots), dim3(256), 0, s,
                        kp, K, M, X, ldx, n, n_pad, U, ldu, m, mp, ca, slab, nrec, sk);
     return;
   }
-  if (v2)
+  if (ca.vi_fold)   // VI: no K u fold in the k-loop, no column sums in the epilogue (KNOT: kept)
+    hipLaunchKernelGGL((k_contract<DT, EPI_GRAD, false, KNOT, false, false, false, true>),
+                       dim3((unsigned)nwg), dim3(256), SGP_CON_SHMEM, s, kp, K, M, X, ldx, n,
+                       n_pad, U, ldu, m, mp, ca, slab, nrec, (double*)nullptr);
+  else if (v2)
     hipLaunchKernelGGL((k_contract<DT, EPI_GRAD, true, KNOT>), dim3((unsigned)nwg), dim3(256), SGP_CON_SHMEM,
                        s, kp, K, M, X, ldx, n, n_pad, U, ldu, m, mp, ca, slab, nrec,
                        (double*)nullptr);
@@ -2426,6 +2463,8 @@ hipError_t launch_contract_args(const KernParams& kp, const double* K, const dou
   *nwg_out = nwg;
   if ((ca.tin2 != nullptr) != (ca.M2 != nullptr) || (ca.tin2 && (!ca.tin || kp.d > 8)))
     return hipErrorInvalidValue;   // the second product: beside a first, with its M, d <= 8
+  if (ca.vi_fold && (ca.tin || ca.beta_in || ca.alpha_in || ca.invz_vec || !ca.uvec || !ca.r))
+    return hipErrorInvalidValue;   // the folded adjoint: VI's operands only
   if (ca.tin != nullptr) {   // stored product: no k-loop (alpha from alpha_in)
     if (ca.uvec != nullptr && ca.alpha_in == nullptr) return hipErrorInvalidValue;
     const bool v2 = ca.beta_in != nullptr, kn = ca.knot_slab != nullptr;

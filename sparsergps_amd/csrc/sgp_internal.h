@@ -197,6 +197,14 @@ struct ConArgs {
   const double* cdiag = nullptr;
   int count_a2 = 0;
   double* alpha_out = nullptr;
+  // VI's folded adjoint G = (r/z) u^T + K P', P' = P - u u^T / z (M is P'): the row factor is
+  // alpha_i = r_i * invz (no K u in the k-loop) and the record's alpha^T alpha field is zero.
+  // With knots fixed (knot_slab == nullptr) the epilogue forms no column sums
+  // C_j = sum_i G_ij K_ij either: the record's e_sig field is zero and the length-scale fields
+  // lack sum_j u~_jc^2 C_j.  The caller adds the missing terms from m x m operands
+  // (launch_vi_fold_cols).  Needs uvec and r; not with beta_in (the two-term epilogue) nor
+  // with tin (stored products).
+  bool vi_fold = false;
   // knot gradient partials (d <= 8): per 128-row tile ti and column j, sum_i G_ij K_ij t_ijc
   // with t = scaled coordinate difference (ARD: (x_c - u_c)/l_c; sqexp/exp: x_c - u_c),
   // written to knot_slab[(ti * mp + j) * d + c]
@@ -277,16 +285,28 @@ hipError_t dense_spd_inverse_sum_chain(const double* A0, double beta, const doub
 // C = a*A + b*B elementwise over mp x mp
 hipError_t dense_axpby(double a, const double* A, double b, const double* B, double* C,
                        int64_t count, hipStream_t s);
-// VI phase 2's m-vectors: the row pass u = invz Binv t, P = a K22inv + b Binv, part_j =
-// sum_k Binv_jk S_jk (part: mp doubles), and the scalars *tu_out = t.u, *trbs_out = sum part
-// (= tr(Binv S)), *rr_out = *rr (one block; only the finish reads them, so they can run on
-// another stream behind the row pass)
+// VI phase 2's m-vectors: the row pass P' = a K22inv + b Binv + c1 u u^T (u given: dense_gemv
+// before it), part_j = sum_k Binv_jk S_jk (part: mp doubles), and the scalars *tu_out = t.u,
+// *trbs_out = sum part (= tr(Binv S)), *rr_out = *rr (one block; only the finish reads them, so
+// they can run on another stream behind the row pass)
 hipError_t launch_vi_mm_rows(const double* Binv, const double* K22inv, const double* S,
-                             const double* t, int64_t mp, double invz, double a, double b,
-                             double* u, double* P, double* part, hipStream_t s);
+                             const double* u, int64_t mp, double a, double b, double c1,
+                             double* P, double* part, hipStream_t s);
 hipError_t launch_vi_mm_scalars(const double* t, const double* u, const double* part, int64_t mp,
                                 const double* rr, double* tu_out, double* trbs_out,
                                 double* rr_out, hipStream_t s);
+// The terms of VI's folded adjoint (ConArgs::vi_fold) that the contraction no longer forms, from
+// the reduced S, t, r^T r and P' = P - u u^T / z (two launches; only the finish reads them):
+//   c_j = sum_i G_ij K_ij = u_j t_j / z + sum_k S_kj P'_kj   (cs: 2 mp doubles of work)
+//   *esig_out = sum_j c_j,  el_out[c] = sum_j u~_jc^2 c_j per length scale (u~ the scaled knot
+//   coordinates; one length scale: summed over the coordinates, times rl2[0]) -- both only
+//   with col_terms (the contraction ran without its column sums), else left untouched;
+//   *ata_out = alpha^T alpha = (r^T r - 2 u^T t + u^T S u) / z^2
+hipError_t launch_vi_fold_cols(const KernParams& kp, const double* S, const double* P,
+                               const double* t, const double* u, const double* U, int64_t ldu,
+                               int64_t m, int64_t mp, double invz, const double* rr, double* cs,
+                               bool col_terms, double* esig_out, double* el_out,
+                               double* ata_out, hipStream_t s);
 // y = scale * A x  (A: mp x mp row-major)
 hipError_t dense_gemv(const double* A, int64_t mp, const double* x, double scale, double* y,
                       hipStream_t s);
