@@ -274,7 +274,9 @@ int sgp_posterior_u(sgp_ctx* ctx, const double* muu, double* u_mean, double* u_v
  *                    GP -- U = xy, u_mean = y, muu = mu, u_var unused (may be NULL)
  * as dispatched by predict_gp (R/laplace_approx_prediction.R:408-542).  u_var is m x m
  * column-major (ld ldv).  pred_var: np values, or with full_cov the np x np matrix
- * (column-major, ld ldpv).  Host buffers; device work space is allocated per call. */
+ * (column-major, ld ldpv).  Host buffers; device work space is allocated per call.
+ * SGP_KERNEL_EXP is refused with SGP_EINVAL before any device work: the reference's fits never
+ * carry that kernel (optimize_gp.R:263), so there is no fitted posterior to predict from. */
 enum { SGP_PRED_VI = 0, SGP_PRED_LAPLACE = 1, SGP_PRED_FULL = 2 };
 int sgp_predict(int device, int kernel, const double* theta, double delta, int method,
                 int gaussian, const double* U, int64_t m, int64_t ldu, const double* u_mean,

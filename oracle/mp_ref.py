@@ -1,4 +1,5 @@
-"""50-digit mpmath restatement of the three objectives -- TEST INFRASTRUCTURE ONLY.
+"""50-digit mpmath restatement of the three objectives and of prediction -- TEST
+INFRASTRUCTURE ONLY.
 
 The third independent pin of the oracle that SURVEY.md 4 / 8(c) prescribes ("mpmath 50-digit
 evaluation at n <= 16").  It shares no code with ``oracle/sgp_oracle.py``: every objective is
@@ -270,3 +271,138 @@ def evaluate(kind, cov_par, cov_fun, X, U, y, mu, delta=1e-6, a=1.0, dps=DPS):
         if kind == "laplace":
             return obj, grad, fhat
         return obj, grad
+
+
+# ----------------------------------------------------------------------------- prediction
+def _abs(M):
+    return M.apply(abs)
+
+
+def _sym_cov(X, th, cov_fun, delta):
+    """Symmetric mode of make_cov_matC / make_cov_mat_ardC (covariance_functionsC.cpp:81-91,
+    133): k(x, x) with tau^2 + delta on the diagonal (i == j only, not on coincident rows)."""
+    S = _cross(X, X, th, cov_fun)
+    for i in range(X.rows):
+        S[i, i] += th["tau"] ** 2 + delta
+    return S
+
+
+def _floats(M, shape=None):
+    import numpy as np
+    a = np.array([[float(M[i, j]) for j in range(M.cols)] for i in range(M.rows)])
+    return a.reshape(shape) if shape is not None else a
+
+
+def _pack(mean, s_mean, var, s_var, full_cov):
+    """mpf results (mp.matrix) plus their fp64 roundings as numpy arrays."""
+    n = mean.rows
+    vshape = (n, n) if full_cov else (n,)
+    return {"pred_mean": _floats(mean, (n,)), "s_mean": _floats(s_mean, (n,)),
+            "pred_var": _floats(var, vshape), "s_var": _floats(s_var, vshape),
+            "mp": {"pred_mean": mean, "s_mean": s_mean, "pred_var": var, "s_var": s_var}}
+
+
+def _mean_and_t(K, S22, dm, u_var):
+    """pred_mean - mu = K w, w = Sigma22^-1 (u_mean - muu) (vi_functions.R:1288,
+    laplace_approx_prediction.R:79, 319), temp22 = -Sigma22^-1 + Sigma22^-1 u_var Sigma22^-1
+    (vi_functions.R:1319, laplace_approx_prediction.R:111; u_var None: the full GP, whose
+    variance is Sigma11 - Sigma12 Sigma22^-1 Sigma21, l.340) and the budgets' |K| forms."""
+    S22i = mp.inverse(S22)
+    w = S22i * dm
+    T = -S22i if u_var is None else -S22i + S22i * u_var * S22i
+    return S22i, K * w, _abs(K) * _abs(w), T
+
+
+def _diag_quad(A, B):
+    """row-wise a_i' B a_i as a column."""
+    AB = A * B
+    return mp.matrix([mp.fsum(AB[i, j] * A[i, j] for j in range(A.cols)) for i in range(A.rows)])
+
+
+def _sparse_predict(method, gaussian, u_mean, u_var, xu, x_pred, cov_fun, cov_par, mu, muu,
+                    full_cov, delta, dps):
+    with mp.workdps(dps):
+        U, Xp, th = _mat(xu), _mat(x_pred), _theta(cov_par)
+        m, n = U.rows, Xp.rows
+        dl = mp.mpf(float(delta))
+        # Sigma22: the gaussian family takes tau^2 off the symmetric filler's diagonal again
+        # (vi_functions.R:1246-1260, laplace_approx_prediction.R:25-43); otherwise it stays
+        # (l.46-62)
+        S22 = _sym_cov(U, th, cov_fun, dl)
+        if gaussian:
+            for j in range(m):
+                S22[j, j] -= th["tau"] ** 2
+        K = _cross(Xp, U, th, cov_fun)
+        dm = _vec(u_mean) - _vec(muu)
+        S22i, kw, kw_abs, T = _mean_and_t(K, S22, dm, _mat(u_var))
+        muv = _vec(mu)
+        mean = muv + kw
+        s_mean = _abs(muv) + kw_abs
+        Ka, Ta = _abs(K), _abs(T)
+        c2 = th["sigma"] ** 2 + th["tau"] ** 2
+        if not full_cov:
+            # vi_functions.R:1321 tau^2 + sigma^2 + delta; laplace_approx_prediction.R:116
+            # sigma^2 + tau^2 (no delta)
+            c0 = c2 + dl if method == "vi" else c2
+            var = _diag_quad(K, T) + c0 * mp.ones(n, 1)
+            s_var = _diag_quad(Ka, Ta) + c0 * mp.ones(n, 1)
+        else:
+            S11 = _sym_cov(Xp, th, cov_fun, dl)
+            KTK = K * T * K.T
+            KTKa = Ka * Ta * Ka.T
+            if method == "vi":
+                var = S11 + KTK                                # vi_functions.R:1313-1315
+                s_var = _abs(S11) + KTKa
+            else:
+                # laplace_approx_prediction.R:103-107: diag(diag(Sigma11 - Q)) + Q + K T K'.
+                # Off the diagonal Sigma11 drops out (terms: Q_ij and K T K'); on it the terms
+                # are Sigma11_ii, -Q_ii and +Q_ii
+                Q = K * S22i * K.T
+                Qa = Ka * _abs(S22i) * Ka.T
+                var = Q + KTK
+                s_var = Qa + KTKa
+                for i in range(n):
+                    var[i, i] = (S11[i, i] - Q[i, i]) + Q[i, i] + KTK[i, i]
+                    s_var[i, i] = abs(S11[i, i]) + 2 * Qa[i, i] + KTKa[i, i]
+        return _pack(mean, s_mean, var, s_var, full_cov)
+
+
+def predict_vi(u_mean, u_var, xu, x_pred, cov_fun, cov_par, mu, muu, full_cov=False,
+               delta=1e-6, dps=DPS):
+    """R/vi_functions.R:1222-1333 (gaussian family) at `dps` digits.  Returns pred_mean /
+    pred_var rounded to fp64 with their budgets s_mean / s_var (numpy), and the mpf originals
+    under "mp"."""
+    return _sparse_predict("vi", True, u_mean, u_var, xu, x_pred, cov_fun, cov_par, mu, muu,
+                           full_cov, delta, dps)
+
+
+def predict_laplace(u_mean, u_var, xu, x_pred, cov_fun, cov_par, mu, muu, full_cov=False,
+                    family="gaussian", delta=1e-6, dps=DPS):
+    """R/laplace_approx_prediction.R:3-123 at `dps` digits (family "gaussian" or any other)."""
+    return _sparse_predict("laplace", family == "gaussian", u_mean, u_var, xu, x_pred, cov_fun,
+                           cov_par, mu, muu, full_cov, delta, dps)
+
+
+def predict_gp_full(xy, y, x_pred, cov_fun, cov_par, mu, mu_pred, full_cov=False, delta=1e-6,
+                    dps=DPS):
+    """R/laplace_approx_prediction.R:281-405 at `dps` digits: Sigma22 = k(xy, xy) +
+    (tau^2 + delta) I, variance Sigma11 - Sigma12 Sigma22^-1 Sigma21 (its diagonal without
+    full_cov, l.359: Sigma11_ii = sigma^2 + tau^2 + delta)."""
+    with mp.workdps(dps):
+        X, Xp, th = _mat(xy), _mat(x_pred), _theta(cov_par)
+        n = Xp.rows
+        dl = mp.mpf(float(delta))
+        S22 = _sym_cov(X, th, cov_fun, dl)
+        K = _cross(Xp, X, th, cov_fun)
+        _, kw, kw_abs, T = _mean_and_t(K, S22, _vec(y) - _vec(mu), None)
+        mup = _vec(mu_pred)
+        Ka, Ta = _abs(K), _abs(T)
+        if full_cov:
+            S11 = _sym_cov(Xp, th, cov_fun, dl)
+            var = S11 + K * T * K.T
+            s_var = _abs(S11) + Ka * Ta * Ka.T
+        else:
+            c0 = th["sigma"] ** 2 + th["tau"] ** 2 + dl
+            var = _diag_quad(K, T) + c0 * mp.ones(n, 1)
+            s_var = _diag_quad(Ka, Ta) + c0 * mp.ones(n, 1)
+        return _pack(mup + kw, _abs(mup) + kw_abs, var, s_var, full_cov)

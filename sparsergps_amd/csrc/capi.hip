@@ -2719,6 +2719,10 @@ int sgp_predict(int device, int kernel, const double* theta, double delta, int m
   KernParams kp;
   int st = make_params(kernel, d, theta, delta, &kp);
   if (st) return st;
+  if (kernel == SGP_KERNEL_EXP) {   // build_knm_range has no 'exp' form; no fit carries it
+    set_err("prediction supports 'sqexp' and 'ard' (optimize_gp.R:263 rejects others)");
+    return SGP_EINVAL;
+  }
   const bool full = method == SGP_PRED_FULL;   // u_var unused (zero): Sigma22 = the data block
   if (!U || m < 1 || ldu < m || !u_mean || !muu || (!u_var && !full) || (!full && ldv < m) ||
       !x_pred || np < 1 ||

@@ -169,6 +169,10 @@ static void einval_checks(void) {
                       buf, 1));
   EINVAL_(sgp_predict(0, 0, th, 1e-6, 9, 1, x, 1, 1, buf, buf, buf, 1, x, 1, 1, 1, buf, 0, buf,
                       buf, 1));
+  /* the 'exp' kernel with otherwise valid arguments: refused before hipSetDevice */
+  EINVAL_(sgp_predict(0, SGP_KERNEL_EXP, th, 1e-6, 0, 1, x, 1, 1, buf, buf, buf, 1, x, 1, 1, 1,
+                      buf, 0, buf, buf, 1));
+  CHECK(strstr(sgp_last_error(), "sqexp") != NULL, "exp refusal message: %s", sgp_last_error());
 #undef EINVAL_
   CHECK(strlen(sgp_last_error()) > 0, "no error message after EINVAL");
 }

@@ -12,6 +12,11 @@ scales, where the reference formula is not the objective's derivative -- is pinn
 
 Problems: n = 14 rows, m = 6 knots (one knot equal to a data row, quirk Q5), d = 2,
 sqexp and ARD.
+
+Prediction (predict_vi, predict_laplace in both families, predict_gp_full; diagonal and
+full_cov) is pinned the same way on the two fixtures of tests/predict_cases.py (m = 24 knots,
+8 rows, two of them equal to knots): every entry of the oracle's output within 1e-10 of that
+entry's magnitude budget s of the 50-digit value.
 """
 import math
 from collections import OrderedDict
@@ -23,7 +28,9 @@ mp = pytest.importorskip("mpmath")
 
 from oracle import mp_ref as M          # noqa: E402
 from oracle import sgp_oracle as O      # noqa: E402
+import predict_cases as PC              # noqa: E402
 
+PRED_ORACLE_TOL = 1e-10                 # of the entry's magnitude budget s
 CASES = [("sqexp", OrderedDict(sigma=1.2, l=1.9, tau=0.6)),
          ("ard", OrderedDict(sigma=1.1, l1=1.6, l2=2.4, tau=0.5))]
 LAP_CASES = [("sqexp", OrderedDict(sigma=1.0, l=2.0, tau=0.3)),
@@ -104,6 +111,36 @@ def test_laplace_length_scale_quirk_is_nonzero():
         c_s = M.laplace_comp3_correction(*args, "sigma", coinc)
     assert abs(float(c_l)) > 1e-3
     assert abs(float(c_s)) < 1e-40
+
+
+# ----------------------------------------------------------------------------- prediction
+@pytest.mark.parametrize("full_cov", [False, True])
+@pytest.mark.parametrize("method", PC.METHODS)
+@pytest.mark.parametrize("name", list(PC.MP_FIXTURES))
+def test_oracle_prediction_matches_mpmath(name, method, full_cov):
+    """Every entry of the fp64 oracle's prediction within 1e-10 of its magnitude budget s
+    (oracle/mp_ref.py) of the 50-digit value.  Measured maxima of |oracle - mpmath| / s over
+    both fixtures and both covariance forms: VI mean 3.0e-15 / variance 7.2e-16,
+    predict_laplace gaussian 3.0e-15 / 3.6e-16, other family 3.3e-16 / 3.4e-16,
+    predict_gp_full 2.4e-16 / 2.5e-16."""
+    ref = PC.mp_predict(name, method, full_cov)
+    got = PC.call(O, method, PC.mp_fixture(name), full_cov)
+    em = np.abs(np.asarray(got["pred_mean"]).reshape(-1) - ref["pred_mean"]) / ref["s_mean"]
+    ev = np.abs(np.asarray(got["pred_var"]) - ref["pred_var"]) / ref["s_var"]
+    print(f"{name} {method} full_cov={full_cov}: mean {em.max():.2e} var {ev.max():.2e}")
+    assert got["pred_var"].shape == ref["pred_var"].shape
+    assert em.max() <= PRED_ORACLE_TOL and ev.max() <= PRED_ORACLE_TOL
+
+
+def test_prediction_budget_bounds_the_value():
+    """s is a sum of absolute values of the terms of its entry: never below |value|, and an
+    off-diagonal entry of a full_cov matrix has a budget of its own, below the diagonal's."""
+    for method in PC.METHODS:
+        r = PC.mp_predict("sqexp_d3", method, True)
+        assert np.all(r["s_var"] >= np.abs(r["pred_var"]) * (1 - 1e-15))
+        assert np.all(r["s_mean"] >= np.abs(r["pred_mean"]) * (1 - 1e-15))
+        off = r["s_var"][~np.eye(8, dtype=bool)]
+        assert off.min() < np.diag(r["s_var"]).min()
 
 
 # ----------------------------------------------------------------------------- GPU
