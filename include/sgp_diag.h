@@ -33,6 +33,15 @@ int sgp_diag_gj_pair(int device, int64_t m, const double* A, const double* B, do
  * one linear stream (pattern 0).  *gbs = the best pass in GB/s (1e9 B/s). */
 int sgp_diag_store_bw(int device, int64_t bytes, int reps, int pattern, double* gbs);
 
+/* Host only (no device is touched): the row-chunk plan a VI evaluation's S = K12^T K12 takes with
+ * n rows and m knots.  *plan: 0 the packed plan (equal chunks, every diagonal 64-block in full),
+ * 1 two chunk lengths (diagonal 128-tiles on longer chunks), 2 the work-balanced plan (every
+ * workgroup the same modelled MFMA count), 3 the m <= 256 kernel; *workgroups: its grid;
+ * *t_balanced, *t_packed: the modelled makespans of the work-balanced and the packed plan in
+ * MFMA slots per wave (*t_balanced = 0 where the work-balanced plan does not apply). */
+int sgp_diag_syrk_plan(int64_t n, int64_t m, int* plan, int* workgroups, double* t_balanced,
+                       double* t_packed);
+
 #ifdef __cplusplus
 }
 #endif

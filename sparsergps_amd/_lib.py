@@ -75,6 +75,8 @@ PROTOTYPES = {
     "sgp_diag_gj_pair": (C.c_int, [C.c_int, C.c_int64, c_double_p, c_double_p, C.c_double, C.c_int,
                                    c_double_p, c_double_p, c_double_p]),
     "sgp_diag_store_bw": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, c_double_p]),
+    "sgp_diag_syrk_plan": (C.c_int, [C.c_int64, C.c_int64, c_int_p, c_int_p, c_double_p,
+                                     c_double_p]),
     "sgp_lap_get_f": (C.c_int, [C.c_void_p, c_double_p]),
     "sgp_lap_get_grad_psi": (C.c_int, [C.c_void_p, c_double_p]),
     "sgp_lap_objective_values": (C.c_int, [C.c_void_p, c_double_p, C.c_int, c_int_p]),

@@ -3236,4 +3236,15 @@ int sgp_diag_store_bw(int device, int64_t bytes, int reps, int pattern, double* 
   return SGP_OK;
 }
 
+int sgp_diag_syrk_plan(int64_t n, int64_t m, int* plan, int* workgroups, double* t_balanced,
+                       double* t_packed) {
+  if (n < 1 || m < 1 || !plan || !workgroups || !t_balanced || !t_packed) {
+    set_err("invalid sgp_diag_syrk_plan arguments");
+    return SGP_EINVAL;
+  }
+  syrk_plan_info(round_up(n, SGP_TILE), round_up(m, SGP_TILE), plan, workgroups, t_balanced,
+                 t_packed);
+  return SGP_OK;
+}
+
 }  // extern "C"

@@ -19,6 +19,7 @@
 
 #include "sgp_internal.h"
 #include "sgp_probe.h"
+#include "sgp_syrk_plan.h"
 
 namespace {
 
@@ -39,10 +40,9 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // bijective XCD-aware remap: work items that share operands get consecutive ids on one XCD
+// (sgp_syrk_plan.h: the SYRK planner's CPU test checks band adjacency through the same function)
 __device__ __forceinline__ int64_t xcd_remap(int64_t orig, int64_t nwg) {
-  const int64_t x = orig % 8, q = nwg / 8, r = nwg % 8;
-  const int64_t base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  return base + orig / 8;
+  return sgp_plan::xcd_remap(orig, nwg);
 }
 
 __device__ __forceinline__ void load8(const double* __restrict__ g, double2 (&v)[4]) {
@@ -152,7 +152,7 @@ __device__ __forceinline__ void mfma_interleave() {
 // rows from the same image -- column tid % 128, the step's rows tid / 128, +2, ... -- and, for
 // t == 0, rr = sum (w r) r or sum tv r (the off-diagonal groups of k_syrk_blk<.., 3, ..> carry
 // no t work).
-template <int V, int WMODE, int TMODE>
+template <int V, int WMODE, int TMODE, bool COMPACT = false>
 __device__ __forceinline__ void syrk_dt_body(const double* __restrict__ K, int64_t mp,
                                              const double* __restrict__ w,
                                              const double* __restrict__ r,
@@ -244,7 +244,8 @@ __device__ __forceinline__ void syrk_dt_body(const double* __restrict__ K, int64
 #undef SDT_GLOAD
 #undef SDT_SSTORE
   tacc = (t4[0] + t4[1]) + (t4[2] + t4[3]);
-  // fragment (R, c) of tile t -> 64-block (2t + R/4, 2t + c/4) of the slab
+  // fragment (R, c) of tile t -> 64-block (2t + R/4, 2t + c/4) of the slab; COMPACT (the
+  // work-balanced plan's partial lists): out holds the tile's 3 lower blocks D0, L, D1 only
 #pragma unroll
   for (int c = 0; c < N1; ++c)
 #pragma unroll
@@ -253,7 +254,8 @@ __device__ __forceinline__ void syrk_dt_body(const double* __restrict__ K, int64
       const int R = hh == 0 ? R0 : R1;
       const d4& a = hh == 0 ? acc0[c] : acc1[c];
       const int rp = 2 * t + R / 4, cp = 2 * t + c / 4;
-      double* blk = out + (int64_t)(rp * (rp + 1) / 2 + cp) * 4096;
+      double* blk = out + (COMPACT ? (int64_t)(R / 4 + c / 4)
+                                   : (int64_t)(rp * (rp + 1) / 2 + cp)) * 4096;
 #pragma unroll
       for (int q = 0; q < 4; ++q)
         blk[((R % 4) * 16 + (lane >> 4) + 4 * q) * 64 + (c % 4) * 16 + (lane & 15)] = a[q];
@@ -533,6 +535,179 @@ k_syrk_blk(const double* __restrict__ K, int64_t n_pad, int64_t mp, const double
         const int col = fn * 16 + (lane & 15);
         out[row * 64 + col] = acc[fm][fn][q];
       }
+}
+
+// ------------------------------------------------- work-balanced unweighted SYRK (VI's S)
+// sgp_syrk_plan.h deals the strictly-lower 128-tile groups in row bands and the diagonal tiles'
+// rows as filler so that every workgroup of the round carries the same modelled MFMA count; a
+// workgroup finds its (at most two) segments with the planner's own syrk_bp_segments.
+//
+// One band chunk of a strictly-lower group: k_syrk_blk<0, 0>'s step (the same operand staging,
+// fragment order and interleave request), wave (wr, wc) = the 64-block (2a + wr, 2b + wc) with
+// rows from image A (K panel a) and columns from image B (panel b); out: the group's 4 blocks.
+__device__ __forceinline__ void syrk_off_seg(const double* __restrict__ K, int64_t mp, int ta,
+                                             int tb, int64_t rbeg, int nsteps,
+                                             double (*Ka)[BK * SB], double (*Kb)[BK * SB],
+                                             double* __restrict__ out) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  d4 acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = d4{0.0, 0.0, 0.0, 0.0};
+  const int lrow = tid >> 4, lc = tid & 15;
+  const double2* gA = reinterpret_cast<const double2*>(K + (rbeg + lrow) * mp + ta * (int64_t)T128) + lc;
+  const double2* gB = reinterpret_cast<const double2*>(K + (rbeg + lrow) * mp + tb * (int64_t)T128) + lc;
+  const int64_t gstep = BK * mp / 2;
+  double2 va0, va1, va2, va3, vb0, vb1, vb2, vb3;
+  const int ro = (wv >> 1) * 64, co = (wv & 1) * 64;
+#define SYRKO_GLOAD(step)                                                       \
+  {                                                                             \
+    const int64_t o_ = (int64_t)(step) * gstep;                                 \
+    va0 = gA[o_]; va1 = gA[o_ + 16]; va2 = gA[o_ + 32]; va3 = gA[o_ + 48];      \
+    vb0 = gB[o_]; vb1 = gB[o_ + 16]; vb2 = gB[o_ + 32]; vb3 = gB[o_ + 48];      \
+  }
+#define SYRKO_SSTORE(buf)                                                       \
+  {                                                                             \
+    double2* pa_ = reinterpret_cast<double2*>(&Ka[buf][lrow * SB]) + lc;        \
+    double2* pb_ = reinterpret_cast<double2*>(&Kb[buf][lrow * SB]) + lc;        \
+    pa_[0] = va0; pa_[16] = va1; pa_[32] = va2; pa_[48] = va3;                  \
+    pb_[0] = vb0; pb_[16] = vb1; pb_[32] = vb2; pb_[48] = vb3;                  \
+  }
+  SYRKO_GLOAD(0);
+  SYRKO_SSTORE(0);
+  __syncthreads();
+  for (int step = 0; step < nsteps; ++step) {
+    const int cur = step & 1;
+    // one basic block per step (mfma_interleave): the last step reloads its own rows into the
+    // idle buffer
+    const bool more = step + 1 < nsteps;
+    SYRKO_GLOAD(more ? step + 1 : step);
+    const double* As = Ka[cur] + ro;
+    const double* Bs = Kb[cur] + co;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const int krow = kk * 4 + (lane >> 4);
+      double af[4], bf[4];
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        af[f] = As[krow * SB + f * 16 + (lane & 15)];
+        bf[f] = Bs[krow * SB + f * 16 + (lane & 15)];
+      }
+#pragma unroll
+      for (int fm = 0; fm < 4; ++fm)
+#pragma unroll
+        for (int fn = 0; fn < 4; ++fn)
+          acc[fm][fn] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[fm], bf[fn], acc[fm][fn], 0, 0, 0);
+    }
+    SYRKO_SSTORE(cur ^ 1);
+    mfma_interleave<false, SGP_SYRK_IL_PAT, 8>();
+    __syncthreads();
+  }
+#undef SYRKO_GLOAD
+#undef SYRKO_SSTORE
+  double* blk = out + (int64_t)wv * 4096;   // local block (wr, wc) = wv
+#pragma unroll
+  for (int fm = 0; fm < 4; ++fm)
+#pragma unroll
+    for (int fn = 0; fn < 4; ++fn)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int row = fm * 16 + (lane >> 4) + 4 * q;
+        const int col = fn * 16 + (lane & 15);
+        blk[row * 64 + col] = acc[fm][fn][q];
+      }
+}
+
+// a run of steps of diagonal tile t (syrk_dt_body: 36 MFMAs per step, the lower fragments only)
+// into one entry of the diagonal partial list
+__device__ __forceinline__ void syrk_diag_seg(const double* __restrict__ K, int64_t mp, int t,
+                                              int64_t rbeg, int nsteps, double (*Ka)[BK * SB],
+                                              double* __restrict__ out) {
+  double tacc = 0.0, rrp = 0.0;
+  switch (threadIdx.x >> 6) {   // wave-uniform
+    case 0: syrk_dt_body<0, 0, 0, true>(K, mp, nullptr, nullptr, nullptr, t, rbeg, nsteps, Ka, nullptr, nullptr, tacc, rrp, out); break;
+    case 1: syrk_dt_body<1, 0, 0, true>(K, mp, nullptr, nullptr, nullptr, t, rbeg, nsteps, Ka, nullptr, nullptr, tacc, rrp, out); break;
+    case 2: syrk_dt_body<2, 0, 0, true>(K, mp, nullptr, nullptr, nullptr, t, rbeg, nsteps, Ka, nullptr, nullptr, tacc, rrp, out); break;
+    default: syrk_dt_body<3, 0, 0, true>(K, mp, nullptr, nullptr, nullptr, t, rbeg, nsteps, Ka, nullptr, nullptr, tacc, rrp, out); break;
+  }
+}
+
+// grid = p.nwg: launch ids [0, p.M) are the band chunks (XCD-remapped, so that the groups of a
+// band sit together), the rest the diagonal-tile workgroups.  Every planned segment has at least
+// one step and ends inside n_pad (syrk_bp_segments; tests/test_syrk_plan.py).
+__global__ void __launch_bounds__(256, 2)
+k_syrk_bal(const double* __restrict__ K, int64_t mp, sgp_plan::SyrkBalPlan p,
+           double* __restrict__ slab_o, double* __restrict__ slab_d) {
+  __shared__ __attribute__((aligned(16))) double Ka[2][BK * SB];
+  __shared__ __attribute__((aligned(16))) double Kb[2][BK * SB];
+  const int wg = (int)blockIdx.x < p.M ? (int)xcd_remap(blockIdx.x, p.M) : (int)blockIdx.x;
+  sgp_plan::SyrkSeg s0, s1;
+  sgp_plan::syrk_bp_segments(p, wg, s0, s1);
+  if (s0.kind == sgp_plan::SEG_OFF) {
+    int ta, tb;
+    sgp_plan::syrk_off_panels(s0.id, ta, tb);
+    syrk_off_seg(K, mp, ta, tb, s0.step0 * BK, s0.nsteps, Ka, Kb,
+                 slab_o + ((int64_t)s0.slab * p.noff + s0.id) * 4 * 4096);
+  } else if (s0.kind == sgp_plan::SEG_DIAG) {
+    syrk_diag_seg(K, mp, s0.id, s0.step0 * BK, s0.nsteps, Ka, slab_d + (int64_t)s0.slab * 3 * 4096);
+  }
+  // a segment's last step ended with a barrier: the images are free.  Second segments are runs
+  // of a diagonal tile: a piece behind a band chunk, or the next tile's head behind a run that
+  // met a tile boundary
+  if (s1.kind == sgp_plan::SEG_DIAG)
+    syrk_diag_seg(K, mp, s1.id, s1.step0 * BK, s1.nsteps, Ka, slab_d + (int64_t)s1.slab * 3 * 4096);
+}
+
+// S from the work-balanced plan's partials: block (rp, cp) of a strictly-lower 128-tile sums its
+// group's p.B band partials, a block of diagonal tile t the tile's list entries
+// [sfirst[t], sfirst[t + 1]) -- ascending rows either way, 16 loads in flight.  Output and the
+// handling of the diagonal blocks' upper fragments as k_syrk_reduce_blk.
+__global__ void __launch_bounds__(256)
+k_syrk_reduce_bal(const double* __restrict__ slab_o, const double* __restrict__ slab_d,
+                  sgp_plan::SyrkBalPlan p, int64_t mp, double* __restrict__ red,
+                  const double* __restrict__ rr_src, double* __restrict__ rr_dst, int packed) {
+  const int64_t bid = blockIdx.y;
+  const int e = blockIdx.x * 256 + threadIdx.x;   // element of the 64 x 64 block
+  if (rr_src && bid == 0 && e < 8) rr_dst[e] = e == 0 ? *rr_src : 0.0;
+  int rp = (int)((sqrtf(8.0f * (float)bid + 1.0f) - 1.0f) * 0.5f);
+  while ((int64_t)(rp + 1) * (rp + 2) / 2 <= bid) ++rp;
+  while ((int64_t)rp * (rp + 1) / 2 > bid) --rp;
+  const int cp = (int)(bid - (int64_t)rp * (rp + 1) / 2);
+  const bool upper = rp == cp && (e / 64) / 16 < (e % 64) / 16;
+  if (upper && !packed) return;
+  if (!packed && rp == cp && (e / 64) < (e % 64)) return;
+  const double* src;
+  int64_t stride;
+  int cnt;
+  if (rp / 2 == cp / 2) {
+    const int t = rp / 2;
+    src = slab_d + ((int64_t)p.sfirst[t] * 3 + (rp & 1) + (cp & 1)) * 4096 + e;
+    stride = 3 * 4096;
+    cnt = p.sfirst[t + 1] - p.sfirst[t];
+  } else {
+    const int a = rp / 2, b = cp / 2, gi = a * (a - 1) / 2 + b;
+    src = slab_o + ((int64_t)gi * 4 + (rp & 1) * 2 + (cp & 1)) * 4096 + e;
+    stride = (int64_t)p.noff * 4 * 4096;
+    cnt = p.B;
+  }
+  double v = 0.0;
+  if (!upper)
+    for (int s0 = 0; s0 < cnt; s0 += 16) {
+      double a[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) a[q] = s0 + q < cnt ? src[(int64_t)(s0 + q) * stride] : 0.0;
+#pragma unroll
+      for (int q = 0; q < 16; ++q)
+        if (s0 + q < cnt) v += a[q];
+    }
+  if (packed) {
+    red[bid * 4096 + e] = v;
+    return;
+  }
+  const int64_t a = (int64_t)rp * 64 + e / 64, b = (int64_t)cp * 64 + e % 64;
+  red[a * mp + b] = v;
+  red[b * mp + a] = v;
 }
 
 // sqrt of non-negative row weights for k_syrk_blk<.., WMODE 2, ..> (NaN for a negative one, which
@@ -1921,37 +2096,10 @@ k_gemm64(int64_t M, int64_t N, int64_t Kd, double alpha, const double* __restric
       }
 }
 
-struct SyrkPlan {
-  int nb, T, splits;
-  int64_t chunk;
-};
+using sgp_plan::SyrkPlan;        // the equal-chunk plans: sgp_syrk_plan.h
+using sgp_plan::syrk_plan;
+using sgp_plan::syrk_plan_blk;
 
-SyrkPlan syrk_plan(int64_t n_pad, int64_t mp) {
-  // One resident "round" = 256 CUs x 2 workgroups (216 VGPRs, 74 KB LDS each).  Pick the
-  // split count so splits * T fills an integer number of rounds as fully as possible.
-  constexpr int64_t kSlots = 512;
-  SyrkPlan p;
-  p.nb = (int)(mp / T128);
-  p.T = p.nb * (p.nb + 1) / 2;
-  const int64_t max_splits = n_pad / BK > 0 ? n_pad / BK : 1;
-  int64_t best = 1;
-  double best_fill = 0.0;
-  for (int64_t rounds = 1; rounds <= 4; ++rounds) {
-    int64_t sp = rounds * kSlots / p.T;
-    if (sp < 1) sp = 1;
-    if (sp > max_splits) sp = max_splits;
-    const double fill = (double)(sp * p.T) / (double)(((sp * p.T + kSlots - 1) / kSlots) * kSlots);
-    if (fill > best_fill + 1e-9) { best_fill = fill; best = sp; }
-    if (best_fill >= 0.95) break;
-  }
-  int64_t chunk = (n_pad + best - 1) / best;
-  chunk = (chunk + BK - 1) / BK * BK;
-  p.chunk = chunk;
-  p.splits = (int)((n_pad + chunk - 1) / chunk);
-  return p;
-}
-
-// k_syrk_blk: the same split rule over its packed groups (T = workgroups per row chunk)
 // Host mirror of syrk_group's image panels (ta, tb) of group gi.
 static void syrk_group_panels(int64_t gi, int nb, int& ta, int& tb) {
   const int64_t noff = (int64_t)nb * (nb - 1) / 2;
@@ -2001,31 +2149,6 @@ static int syrk_t_table(int nb, int ngroups, int* tmap) {
   return 0;   // no placement (does not happen for nb >= 1: S = 1 needs nb distinct holders)
 }
 
-SyrkPlan syrk_plan_blk(int64_t n_pad, int64_t mp) {
-  SyrkPlan p = syrk_plan(n_pad, mp);   // nb, and a starting point
-  const int nb = p.nb;
-  const int groups = nb * (nb - 1) / 2 + (3 * nb + 3) / 4;
-  constexpr int64_t kSlots = 512;
-  const int64_t max_splits = n_pad / BK > 0 ? n_pad / BK : 1;
-  int64_t best = 1;
-  double best_fill = 0.0;
-  for (int64_t rounds = 1; rounds <= 4; ++rounds) {
-    int64_t sp = rounds * kSlots / groups;
-    if (sp < 1) sp = 1;
-    if (sp > max_splits) sp = max_splits;
-    const double fill = (double)(sp * groups) /
-                        (double)(((sp * groups + kSlots - 1) / kSlots) * kSlots);
-    if (fill > best_fill + 1e-9) { best_fill = fill; best = sp; }
-    if (best_fill >= 0.95) break;
-  }
-  int64_t chunk = (n_pad + best - 1) / best;
-  chunk = (chunk + BK - 1) / BK * BK;
-  p.T = groups;
-  p.chunk = chunk;
-  p.splits = (int)((n_pad + chunk - 1) / chunk);
-  return p;
-}
-
 // Balanced plan (nb >= 3): the strictly-lower 128-tiles as k_syrk_blk's packed groups with S_o
 // row chunks (64 MFMAs per wave-step), the nb diagonal 128-tiles as syrk_dtile workgroups with
 // S_d longer chunks (36 MFMAs per wave-step, no redundant upper fragments), one residency round
@@ -2033,8 +2156,10 @@ SyrkPlan syrk_plan_blk(int64_t n_pad, int64_t mp) {
 // per-fragment weights and the t slice where they apply).  Unweighted or sqrt(w)-staged S:
 // used when its makespan, max(64 chunk_o, wd chunk_d), beats the packed plan's 64 chunk by
 // more than 2 % (C5's m = 512: 1.143 -> 1.049 n MFMA-steps per row; at m = 1024 the round's
-// integer split counts leave no gain).  force (signed weights or t, WMODE 3): always -- there
-// it moves the per-fragment weights and the t slice off the off-diagonal groups.
+// integer split counts leave no gain: two chunk lengths cannot fill 512 slots evenly there, which
+// is what the unweighted S has sgp_syrk_plan.h's work-balanced plan for -- syrk_plan_wb below;
+// this one stays for the sqrt(w)-staged S).  force (signed weights or t, WMODE 3): always --
+// there it moves the per-fragment weights and the t slice off the off-diagonal groups.
 struct SyrkBal {
   bool on = false;
   int S_o = 0, S_d = 0;
@@ -2082,6 +2207,22 @@ static SyrkBal syrk_plan_bal(int64_t n_pad, int64_t mp, double wd, bool force) {
   return b;
 }
 
+// The unweighted S without t (VI): the work-balanced plan (sgp_syrk_plan.h, k_syrk_bal) when it
+// beats the packed plan's modelled makespan by more than 2 %; it declines for nb < 3 and m > 3968.
+static sgp_plan::SyrkBalPlan syrk_plan_wb(int64_t n_pad, int64_t mp) {
+  if (!SGP_SYRK_WB) return sgp_plan::SyrkBalPlan{};
+  // the search takes 20-100 us of host time and an evaluation asks twice (kernel, reduction)
+  // with the same shape: the calling thread's last plan is kept
+  thread_local int64_t last_n = -1, last_mp = -1;
+  thread_local sgp_plan::SyrkBalPlan last{};
+  if (last_n != n_pad || last_mp != mp) {
+    last = sgp_plan::syrk_plan_balanced(n_pad, mp, SGP_SYRK_WB_SLOTS, (double)SGP_SDT_W);
+    last_n = n_pad;
+    last_mp = mp;
+  }
+  return last;
+}
+
 // k_syrk_s256 (mp = 256): two workgroups per row chunk, as many chunks as fill one residency
 // round
 static SyrkPlan syrk_plan_s256(int64_t n_pad) {
@@ -2122,6 +2263,8 @@ int64_t syrk_slab_doubles_mp(int64_t n_pad, int64_t mp) {
       need = std::max(need, (int64_t)(bal.S_o + bal.S_d) * nblk * 4096 +
                                 (int64_t)std::max(bal.S_o, bal.S_d) * (q.nb * T128 + 1) + n_pad);
   }
+  const sgp_plan::SyrkBalPlan wb = syrk_plan_wb(n_pad, mp);
+  if (wb.on) need = std::max(need, sgp_plan::syrk_bp_slab_doubles(wb));
   if (mp == 256) {
     SyrkPlan r = syrk_plan_s256(n_pad);
     need = std::max(need, (int64_t)r.splits * (10 * 4096 + 2 * T128 + 1) + n_pad);   // as laid out
@@ -2146,6 +2289,25 @@ hipError_t launch_syrk_aug(const double* K, int64_t n_pad, int64_t mp, const dou
   {   // the packed 64-block kernel (no redundant diagonal-tile halves), or at mp = 256 the
       // fragment-balanced k_syrk_s256 (same slab layout and reduction)
     const bool s256 = syrk_use_s256(mp, with_t != 0);
+    if (!s256 && !with_t && !w) {
+      // VI's S: the work-balanced plan, its partials reduced in the planner's order
+      const sgp_plan::SyrkBalPlan wb = syrk_plan_wb(n_pad, mp);
+      if (wb.on) {
+        if (sgp_plan::syrk_bp_slab_doubles(wb) > slab_cap) return hipErrorInvalidValue;
+        double* sl_o = slab;
+        double* sl_d = slab + sgp_plan::syrk_bp_off_doubles(wb);
+        if (part & 1)
+          hipLaunchKernelGGL(k_syrk_bal, dim3((unsigned)wb.nwg), dim3(256), 0, s, K, mp, wb, sl_o,
+                             sl_d);
+        if (part & 2) {
+          const int64_t nblk = (int64_t)(2 * wb.nb) * (2 * wb.nb + 1) / 2;
+          hipLaunchKernelGGL(k_syrk_reduce_bal, dim3(4096 / 256, (unsigned)nblk), dim3(256), 0, s,
+                             sl_o, sl_d, wb, mp, red, rr_src,
+                             red + (packed ? nblk * 4096 : mp * mp) + mp, packed ? 1 : 0);
+        }
+        return hipGetLastError();
+      }
+    }
     SyrkPlan q = s256 ? syrk_plan_s256(n_pad) : syrk_plan_blk(n_pad, mp);
     // nb >= 3: signed weights or t -> WMODE 3 on the balanced plan (the off-diagonal groups
     // stage w o K as their A image and carry no t; the diagonal tiles keep the per-fragment
@@ -2265,6 +2427,26 @@ hipError_t launch_syrk_aug(const double* K, int64_t n_pad, int64_t mp, const dou
                            sl_t, sl_rr, t_splits, q.nb, mp, red);
     }
     return hipGetLastError();
+  }
+}
+
+// which plan launch_syrk_aug takes for the unweighted S without t (sgp_diag_syrk_plan)
+void syrk_plan_info(int64_t n_pad, int64_t mp, int* plan, int* nwg, double* t_bal,
+                    double* t_pack) {
+  const sgp_plan::SyrkBalPlan wb = syrk_plan_wb(n_pad, mp);
+  *t_bal = wb.T_bal;
+  *t_pack = wb.T_pack;
+  if (syrk_use_s256(mp, false)) {
+    *plan = 3;
+    *nwg = syrk_plan_s256(n_pad).splits * 2;
+  } else if (wb.on) {
+    *plan = 2;
+    *nwg = wb.nwg;
+  } else {
+    const SyrkBal bal = syrk_plan_bal(n_pad, mp, syrk_dtile_cost(false, false), false);
+    const SyrkPlan q = syrk_plan_blk(n_pad, mp);
+    *plan = bal.on ? 1 : 0;
+    *nwg = bal.on ? bal.S_o * (q.nb * (q.nb - 1) / 2) + bal.S_d * q.nb : q.splits * q.T;
   }
 }
 

@@ -172,6 +172,10 @@ hipError_t launch_syrk_aug(const double* K, int64_t n_pad, int64_t mp, const dou
 int64_t syrk_packed_doubles(int64_t mp);
 hipError_t launch_unpack_lower64(const double* packed, int64_t mp, double* S, hipStream_t s);
 int64_t syrk_slab_doubles(int64_t n_pad, int64_t mp);
+// the plan of the unweighted S without t at (n_pad, mp): 0 packed, 1 two chunk lengths
+// (syrk_plan_bal), 2 work-balanced (sgp_syrk_plan.h), 3 k_syrk_s256; its workgroups; the
+// work-balanced and the packed plan's modelled makespans in MFMA slots
+void syrk_plan_info(int64_t n_pad, int64_t mp, int* plan, int* nwg, double* t_bal, double* t_pack);
 // true when launch_syrk_aug uses the fragment-balanced mp = 256 kernel (S only)
 bool syrk_use_s256(int64_t mp, bool with_t);
 // Gradient contraction on T = K M (K: n_pad x mp, M: mp x mp):

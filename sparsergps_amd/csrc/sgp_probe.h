@@ -20,6 +20,8 @@
 //   SGP_CON_IL_SPREAD   contraction: LDS fragment reads spread over the step instead of up front
 //   SGP_CON_SHMEM       dynamic LDS pad of the gradient-contraction launches
 //   SGP_SYRK_BAL        0: no balanced S-only SYRK plan (syrk_plan_bal)
+//   SGP_SYRK_WB         0: VI's unweighted S without the work-balanced plan (sgp_syrk_plan.h)
+//   SGP_SYRK_WB_SLOTS   workgroup slots the work-balanced plan fills (512: the whole round)
 //   SGP_SDT_IL          0: the diagonal-tile SYRK step without the interleave request
 //   SGP_SDT_W           syrk_plan_bal's cost of a diagonal-tile wave-step, in MFMAs (36 issued)
 //   SGP_SDT_WW          ... plus this with per-fragment weights
@@ -46,7 +48,8 @@
 #if (defined(SGP_CON_TRACE) || defined(SGP_CON_NO_EPILOGUE) || defined(SGP_GJ_TRACE) ||       \
      defined(SGP_IL_VMEM0) || defined(SGP_CON_IL_PAT) || defined(SGP_SYRK_IL_PAT) ||          \
      defined(SGP_CON_IL_SPREAD) || defined(SGP_CON_SHMEM) ||                                  \
-     defined(SGP_SYRK_BAL) || defined(SGP_SDT_IL) || defined(SGP_S256_IL) ||                  \
+     defined(SGP_SYRK_BAL) || defined(SGP_SYRK_WB) || defined(SGP_SYRK_WB_SLOTS) ||           \
+     defined(SGP_SDT_IL) || defined(SGP_S256_IL) ||                  \
      defined(SGP_SDT_W) || defined(SGP_SDT_WW) || defined(SGP_SDT_WT) ||                      \
      defined(SGP_SYRK_W3) || defined(SGP_CON_ROWQ_KU) ||                                      \
      defined(SGP_LAP_RS_CFG) || defined(SGP_GJ_MM_UNROLL) || defined(SGP_VI_BUILD_NO_T) ||        \
@@ -81,6 +84,12 @@
 #endif
 #ifndef SGP_SYRK_BAL
 #define SGP_SYRK_BAL 1
+#endif
+#ifndef SGP_SYRK_WB
+#define SGP_SYRK_WB 1
+#endif
+#ifndef SGP_SYRK_WB_SLOTS
+#define SGP_SYRK_WB_SLOTS 512
 #endif
 #ifndef SGP_SDT_IL
 #define SGP_SDT_IL 1
