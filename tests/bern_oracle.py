@@ -4,7 +4,8 @@
   grad_loglik_fn_bern       R/derivative_functions_of_data_likelihoods.R:186-235
   obj_fun_bern              R/laplace_approx_obj_funs.R:189-341
   newtrap_sparseGP          R/newtrap_sparseGP.R:6-186 (+ _update 234-325) with those helpers
-  dlogq_dcov_par            R/laplace_approx_gradient.R:25-336 with those helpers (knots fixed)
+  dlogq_dcov_par            R/laplace_approx_gradient.R:25-553 with those helpers (theta loop and
+                            knot closure)
 
 The matrix algebra is the Poisson path's and comes from oracle.sgp_oracle (laplace_mats, r_chol,
 r_solve, _dmats, a1_diag, _gaussian_comps, laplace_posterior_u); only the four likelihood
@@ -147,8 +148,12 @@ def stop_margins(stop_trace, tol):
     return abs(q[-1] - tol) / tol, (abs(q[-2] - tol) / tol if q.size > 1 else math.inf)
 
 
-def dlogq_dcov_par(cov_par, cov_fun, xu, xy, y, ff, mu, delta=1e-6):
-    """laplace_approx_gradient.R:25-336 with the Bernoulli d1, d2, d3 (knots fixed)."""
+def dlogq_dcov_par_with(d1_fn, d2_fn, d3_fn, cov_par, cov_fun, xu, xy, y, ff, mu, delta=1e-6,
+                        dcov_fun_dknot=None, knot_opt=None):
+    """laplace_approx_gradient.R:25-553 with the likelihood derivatives d{1,2,3}_fn(ff, y) passed
+    in: the theta loop (l.25-336) and the knot closure (l.341-543, that of O.dlogq_dcov_par).
+    Nothing else depends on the family, so with the Poisson derivatives this reproduces
+    O.dlogq_dcov_par bit for bit (tests/test_knot_oracle.py)."""
     y = np.asarray(y, dtype=np.float64).reshape(-1)
     mu = np.asarray(mu, dtype=np.float64).reshape(-1)
     ff = np.asarray(ff, dtype=np.float64).reshape(-1)
@@ -158,14 +163,14 @@ def dlogq_dcov_par(cov_par, cov_fun, xu, xy, y, ff, mu, delta=1e-6):
     Sigma12, Sigma22 = O._cov_mats(cov_par, cov_fun, xu, xy, delta, lnames)   # l.92-120
     FF = O.r_solve(Sigma22, Sigma12.T)
     Z = float(cov_par["sigma"]) ** 2 + float(cov_par["tau"]) ** 2 + delta - np.sum(Sigma12 * FF.T, axis=1)
-    W = d2log_py_dff_bern(ff, y)
+    W = d2_fn(ff, y)
     B = 1 / (Z - (1 / W))                                                 # l.133
     R = O.r_chol(Sigma22 + Sigma12.T @ ((1 / Z)[:, None] * Sigma12))
-    W3 = d3log_py_dff_bern(ff, y)
+    W3 = d3_fn(ff, y)
     C = O.r_solve(Sigma22 + Sigma12.T @ (B[:, None] * Sigma12))
     ZS = (1 / Z)[:, None] * Sigma12
     comp2_1 = (1 / Z) * (ff - mu) - O.r_solve(R, O.r_solve(R.T, ZS.T)).T @ (ZS.T @ (ff - mu))
-    grad_log_py_ff = dlog_py_dff_bern(ff, y)
+    grad_log_py_ff = d1_fn(ff, y)
     GG = O.r_solve(Sigma22, Sigma12.T @ grad_log_py_ff)                   # l.155
     D = W - 1 / Z                                                         # l.161
     E2 = np.eye(Sigma22.shape[0]) + O.r_solve(R.T, ZS.T) @ \
@@ -187,7 +192,26 @@ def dlogq_dcov_par(cov_par, cov_fun, xu, xy, y, ff, mu, delta=1e-6):
         BS12 = B[:, None] * Sigma12
         comp3 = -(1 / W) * (B * comp3_1) + (1 / W) * (BS12 @ (C @ (Sigma12.T @ (B * comp3_1))))  # l.313-314
         grad[par_name] = float(0.5 * comp2 - 0.5 * comp1 - 0.5 * ((comp4 * (-W3)) @ comp3))      # l.334-336
+    if dcov_fun_dknot is not None:                                        # l.341-543
+
+        def one(d12, d22):
+            A = -np.sum((2 * d12 - FF.T @ d22) * FF.T, axis=1)
+            comp1, comp2 = O._gaussian_comps(A, B, C, FF, Sigma12, Sigma22, d12, d22, comp2_1)
+            c31 = A * grad_log_py_ff + 2 * d12 @ GG - FF.T @ d22 @ GG
+            BS12 = B[:, None] * Sigma12
+            c3 = -(1 / W) * (B * c31) + (1 / W) * (BS12 @ (C @ (Sigma12.T @ (B * c31))))
+            return float(0.5 * comp2 - 0.5 * comp1 - 0.5 * ((comp4 * (-W3)) @ c3))
+        gk, tk = O._knot_loop(xu, xy, cov_par, dcov_fun_dknot, knot_opt, one)
+        return {"gradient": grad, "knot_gradient": gk, "trans_knot": tk}
     return {"gradient": grad}
+
+
+def dlogq_dcov_par(cov_par, cov_fun, xu, xy, y, ff, mu, delta=1e-6, dcov_fun_dknot=None,
+                   knot_opt=None):
+    """laplace_approx_gradient.R:25-553 with the Bernoulli d1, d2, d3; dcov_fun_dknot ("sqexp" /
+    "ard") adds "knot_gradient" and "trans_knot" for the knots of knot_opt (None: all)."""
+    return dlogq_dcov_par_with(dlog_py_dff_bern, d2log_py_dff_bern, d3log_py_dff_bern, cov_par,
+                               cov_fun, xu, xy, y, ff, mu, delta, dcov_fun_dknot, knot_opt)
 
 
 def laplace_grad_ascent(cov_par_start, cov_fun, xu, xy, y, ff, mu, muu, opt=None):
