@@ -27,6 +27,8 @@
  *   sgp_eval_laplace <- newtrap_sparseGP (R/newtrap_sparseGP.R:6-186) + dlogq_dcov_par
  *                      (R/laplace_approx_gradient.R:25-553), Poisson likelihood or, after
  *                      sgp_lap_set_family, Bernoulli
+ *   sgp_eval_full_laplace <- newtrapGP (R/newtrapGP.R:6-177) + dlogq_dcov_par_full
+ *                      (R/laplace_approx_gradient.R:558-711), the same two families
  *
  * Hyperparameters are passed as `theta` laid out [sigma, l_1..l_L, tau] with
  * L = 1 (sqexp, exp) or L = d (ard).  Gradients are d/d log(theta) in that order
@@ -123,7 +125,8 @@ int sgp_ctx_destroy(sgp_ctx* ctx);
  * sgp_ctx_set_data, sgp_ctx_rows (all rows), the three candidate scorers (each VI candidate as an
  * objective-only evaluation at [U; cand_t], m + 1 <= m_max), the timing calls (shard 0's
  * record) and sgp_ctx_destroy.  The phase-level entry points (sgp_vi_phase1 ... sgp_lap_step),
- * sgp_ctx_set_stream, sgp_ctx_set_packed_reduction and sgp_eval_full return SGP_EINVAL.
+ * sgp_ctx_set_stream, sgp_ctx_set_packed_reduction, sgp_eval_full, sgp_eval_full_laplace and
+ * sgp_full_laplace_state return SGP_EINVAL.
  * 1 <= nshards <= min(n, 64). */
 int sgp_ctx_create_multi(sgp_ctx** out, const int* devices, int nshards, const double* X,
                          int64_t n, int64_t ldx, int d, const double* y, const double* mu,
@@ -260,6 +263,35 @@ int sgp_lap_nr(sgp_ctx* ctx, int kernel, const double* theta, const double* U, i
 int sgp_eval_full(sgp_ctx* ctx, int kernel, const double* theta, double delta, unsigned flags,
                   double* obj, double* grad);
 
+/* Full (non-sparse) Laplace GP over the context's n rows for the Poisson or Bernoulli family
+ * (optimize_gp.R:687-732; requires m_max >= n; SGP_KERNEL_EXP and multi-device contexts are
+ * refused as by sgp_eval_full): one evaluation = newtrapGP warm-started from the context's
+ * resident f (R/newtrapGP.R:6-177 with obj_fun_pois_full / obj_fun_bern_full,
+ * R/laplace_approx_obj_funs.R:67-102, 346-397, and grad_loglik_fn_pois_full / _bern_full,
+ * R/derivative_functions_of_data_likelihoods.R:65-84, 239-267) followed by dlogq_dcov_par_full at
+ * the mode (R/laplace_approx_gradient.R:558-711), exactly as one iteration of
+ * laplace_grad_ascent_full (R/laplace_gradient_ascent.R:742-771, 957-985).
+ * Sigma = k(xy, xy) + (tau^2 + delta) I.  Family, exposure and f are the context's resident ones
+ * (sgp_lap_set_family, sgp_lap_set_expo / expo as for sgp_eval_laplace, sgp_lap_set_f /
+ * sgp_lap_get_f); the mode stays resident and warm-starts the next evaluation.  tol / maxit =
+ * tol_nr / maxit_nr: the first update always runs (newtrapGP.R:63-75), then the loop continues
+ * while iter < maxit && (|obj_k - obj_{k-1}| > tol || any(|grad psi| > tol)) (l.77) with
+ * grad psi = d1 - Sigma^-1 (f - mu) at the iterate the last update started from.  maxit = 0
+ * skips the NR loop: objective and dlogq_dcov_par_full at the resident f as given.
+ * obj = the last NR objective value; nr_iters = length(objective_function_values) (may be NULL).
+ * SGP_FLAG_OBJ_ONLY is newtrapGP alone (grad may be NULL).  sgp_lap_objective_values and
+ * sgp_lap_get_grad_psi serve this path as they serve the sparse one.  SGP_ENOTPD names the
+ * matrix (Sigma, or I + sqrt(-W) Sigma sqrt(-W)) that is not positive definite or not finite. */
+int sgp_eval_full_laplace(sgp_ctx* ctx, int kernel, const double* theta, double delta,
+                          double expo, double tol, int maxit, unsigned flags, double* obj,
+                          double* grad, int* nr_iters);
+/* newtrapGP's returned `W` and `grad_log_py_ff` (R/newtrapGP.R:96-99), n host values each: the
+ * likelihood's second and first derivatives at the iterate the LAST UPDATE STARTED FROM, not at
+ * the returned mode, as the reference's loop leaves them (l.69-72, 83-86) and as
+ * predict_laplace_full consumes them.  SGP_EINVAL unless a full-Laplace NR step has run since
+ * the mode was last set (a maxit = 0 evaluation takes no step). */
+int sgp_full_laplace_state(sgp_ctx* ctx, double* W, double* grad_log_py_ff);
+
 /* Posterior of the knot values u at the end of a fit, from the context's last completed
  * evaluation (VI: vi_functions.R:1161-1180; FITC: laplace_gradient_ascent.R:1635-1655;
  * Laplace: newtrap_sparseGP.R:137-176).  muu, u_mean: m host values; u_var: m x m host,
@@ -272,12 +304,22 @@ int sgp_posterior_u(sgp_ctx* ctx, const double* muu, double* u_mean, double* u_v
  *                    gaussian != 0 selects the family == "gaussian" Sigma22)
  *   SGP_PRED_FULL    predict_gp_full (R/laplace_approx_prediction.R:281-405): a full Gaussian
  *                    GP -- U = xy, u_mean = y, muu = mu, u_var unused (may be NULL)
+ *   SGP_PRED_LAPLACE_FULL predict_laplace_full (R/laplace_approx_prediction.R:128-214): a full
+ *                    Poisson / Bernoulli Laplace fit -- U = xy, u_mean = grad_log_py_ff and
+ *                    muu = W as sgp_full_laplace_state returns them (every W <= 0, else
+ *                    SGP_EINVAL), u_var unused (may be NULL):
+ *                      pred_mean = mu_pred + k(x_pred, xy) grad_log_py_ff                (l.209)
+ *                      pred_var  = Sigma11(x_pred) - k(x_pred, xy) R k(xy, x_pred),
+ *                                  R = sqrt(-W) (I + sqrt(-W) Sigma sqrt(-W))^-1 sqrt(-W)
+ *                                  (= t(v) %*% v, l.169, 188, 206)
+ *                    The reference defines pred_mean only when full_cov is FALSE (l.190-210) and
+ *                    fails otherwise; here the mean is returned in both forms.
  * as dispatched by predict_gp (R/laplace_approx_prediction.R:408-542).  u_var is m x m
  * column-major (ld ldv).  pred_var: np values, or with full_cov the np x np matrix
  * (column-major, ld ldpv).  Host buffers; device work space is allocated per call.
  * SGP_KERNEL_EXP is refused with SGP_EINVAL before any device work: the reference's fits never
  * carry that kernel (optimize_gp.R:263), so there is no fitted posterior to predict from. */
-enum { SGP_PRED_VI = 0, SGP_PRED_LAPLACE = 1, SGP_PRED_FULL = 2 };
+enum { SGP_PRED_VI = 0, SGP_PRED_LAPLACE = 1, SGP_PRED_FULL = 2, SGP_PRED_LAPLACE_FULL = 3 };
 int sgp_predict(int device, int kernel, const double* theta, double delta, int method,
                 int gaussian, const double* U, int64_t m, int64_t ldu, const double* u_mean,
                 const double* muu, const double* u_var, int64_t ldv, const double* x_pred,

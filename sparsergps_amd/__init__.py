@@ -8,8 +8,9 @@ from ._lib import NotPositiveDefinite, SGPError
 from .covariance import (cov_fun_expC, cov_fun_sqrd_exp_ardC, cov_fun_sqrd_expC, dsig_dtheta_ardC,
                          dsig_dthetaC, make_cov_mat_ardC, make_cov_matC)
 from .drivers import laplace_grad_ascent, norm_grad_ascent, norm_grad_ascent_vi
-from .full import (dlogp_dcov_par_full, full_eval, norm_grad_ascent_full, obj_fun_norm_full,
-                   predict_gp_full)
+from .full import (dlogp_dcov_par_full, dlogq_dcov_par_full, full_eval, full_laplace_eval,
+                   laplace_grad_ascent_full, newtrapGP, norm_grad_ascent_full, obj_fun_bern_full,
+                   obj_fun_norm_full, obj_fun_pois_full, predict_gp_full, predict_laplace_full)
 from .predict import predict_gp, predict_laplace, predict_vi
 from .laplace import (dlogq_dcov_par, laplace_eval, newtrap_sparseGP, obj_fun_bern,
                       obj_fun_pois)
@@ -27,4 +28,6 @@ __all__ = [
     "norm_grad_ascent_vi", "norm_grad_ascent", "laplace_grad_ascent",
     "full_eval", "obj_fun_norm_full", "dlogp_dcov_par_full", "norm_grad_ascent_full",
     "predict_gp_full",
+    "full_laplace_eval", "newtrapGP", "obj_fun_pois_full", "obj_fun_bern_full",
+    "dlogq_dcov_par_full", "laplace_grad_ascent_full", "predict_laplace_full",
 ]

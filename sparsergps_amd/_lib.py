@@ -21,7 +21,7 @@ SGP_OK, SGP_EINVAL, SGP_ENOTPD, SGP_EHIP, SGP_ENOMEM = 0, 1, 2, 3, 4
 KERNELS = {"sqexp": 0, "ard": 1, "exp": 2}
 SGP_FLAG_R_DET = 1
 SGP_FLAG_OBJ_ONLY = 2
-SGP_PRED_VI, SGP_PRED_LAPLACE, SGP_PRED_FULL = 0, 1, 2
+SGP_PRED_VI, SGP_PRED_LAPLACE, SGP_PRED_FULL, SGP_PRED_LAPLACE_FULL = 0, 1, 2, 3
 SGP_EXPO_ROWS = 0.0   # expo argument: the per-row exposure of sgp_lap_set_expo
 FAMILIES = {"poisson": 0, "bernoulli": 1}   # SGP_FAM_*: sgp_lap_set_family
 
@@ -93,6 +93,10 @@ PROTOTYPES = {
                              C.c_double, C.c_double, C.c_double, C.c_int, c_double_p, c_int_p]),
     "sgp_eval_full": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_double, C.c_uint,
                                 c_double_p, c_double_p]),
+    "sgp_eval_full_laplace": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_double, C.c_double,
+                                        C.c_double, C.c_int, C.c_uint, c_double_p, c_double_p,
+                                        c_int_p]),
+    "sgp_full_laplace_state": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "sgp_posterior_u": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
     "sgp_predict": (C.c_int, [C.c_int, C.c_int, c_double_p, C.c_double, C.c_int, C.c_int, c_double_p,
                               C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int64,

@@ -316,6 +316,9 @@ struct sgp_ctx {
   const double* lap_av = nullptr;         // this NR run's per-row exposure (nullptr: lap_expo)
   int lap_family = SGP_FAM_POISSON;       // sgp_lap_set_family
   std::vector<double> lap_objs;           // objective_function_values of the last NR run
+  // full-GP Laplace (sgp_eval_full_laplace): FL_N x n_pad row vectors, allocated on first use
+  double* fl = nullptr;
+  bool fl_valid = false;                  // FL_W0 / FL_D10 hold a full-Laplace NR's returned state
   // timing
   bool timing = false;
   std::string timing_only;                // record only the scopes of this name ("" = all)
@@ -515,7 +518,7 @@ void ctx_free(sgp_ctx* c) {
                   c->sk_ws,  c->sk_flags,
                   c->Xt22,   c->T22,    c->dinv22, c->omega, c->pvec, c->rowq, c->red2f,
                   c->y,      c->mu,     c->lv,     c->lm,    c->lslab, c->lred[0], c->lred[1],
-                  c->Cprev,  c->lapAZ,  c->lapAB,  c->laprv,
+                  c->Cprev,  c->lapAZ,  c->lapAB,  c->laprv,  c->fl,
                   c->knot_slab, c->knot_part, c->knot_kmm, c->tslab, c->tq, c->tp,
                   c->rr_dev, c->Sfull, c->gjs, c->mmpart, c->rsync};
   for (void* p : ptrs)
@@ -648,6 +651,7 @@ void sgp_internal_set_err(const char* msg) { set_err("%s", msg); }
 void sgp_internal_forget_eval(sgp_ctx* c) {
   c->last_mode = 0;
   c->lap_gpsi_valid = false;
+  c->fl_valid = false;
 }
 
 hipStream_t sgp_internal_stream(sgp_ctx* c) { return c->stream; }
@@ -2015,6 +2019,7 @@ int sgp_lap_set_f(sgp_ctx* c, const double* f, double fill) {
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipMemcpy(lvec(c, LV_F), h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
   c->lap_gpsi_valid = false;
+  c->fl_valid = false;
   return SGP_OK;
 }
 
@@ -2182,6 +2187,7 @@ int sgp_lap_begin(sgp_ctx* c, int kernel, const double* theta, const double* U, 
   c->lap_it = 0;
   c->lap_cnt = 0.0;
   c->lap_gpsi_valid = false;   // grad psi belongs to the NR run that starts here
+  c->fl_valid = false;
   c->lap_objs.clear();
   const int64_t mp = c->mp;
   st = upload_knots(c, U, m, ldu);
@@ -2656,6 +2662,239 @@ int sgp_eval_full(sgp_ctx* c, int kernel, const double* theta, double delta, uns
   return SGP_OK;
 }
 
+// ------------------------------------------------------------------------- full-GP Laplace
+// family = "poisson" / "bernoulli" with sparse = FALSE (optimize_gp.R:687-732): one evaluation is
+// newtrapGP (R/newtrapGP.R:6-177) from the resident f followed by dlogq_dcov_par_full
+// (R/laplace_approx_gradient.R:558-711) at the mode, as one iteration of
+// laplace_grad_ascent_full (R/laplace_gradient_ascent.R:742-771, 957-985).
+//   Sigma = k(xy, xy) + (tau^2 + delta) I and Sigma^-1 come from the K22 stage, once per theta.
+//   State at f:  B = I + sW Sigma sW (sW = sqrt(-W)), b = -W (f - mu) + d1,
+//                a = b - sW o (B^-1 (sW o (Sigma b)))                      (newtrapGP.R:163-170)
+//   objective:   -1/2 a^T (f - mu) + log p(y | f) - 1/2 log det B  (obj_fun_pois_full l.85-100)
+//   Newton step: f <- Sigma a + mu                                         (newtrapGP.R:172)
+//   grad psi:    d1 - Sigma^-1 (f - mu)  (grad_loglik_fn_pois_full l.78-83: a real solve)
+// One inverse of B serves the objective at f, the step taken from f and, at the last f, the
+// gradient: R = sW B^-1 sW, s2 = 1/2 (diag Sigma - diag(Sigma R Sigma)) o W3,
+// v = s2 - R Sigma s2 and grad_p = sum_ij G_ij (dSigma_p)_ij with
+// G = 1/2 a a^T - 1/2 R + 1/2 (v d1^T + d1 v^T) (the adjoint of l.693-706).
+enum { FL_W = 0, FL_D1, FL_W0, FL_D10, FL_SW, FL_W3, FL_B, FL_RF, FL_Q, FL_GP, FL_T2, FL_A, FL_Y,
+       FL_S2, FL_TMP, FL_V, FL_N };   // (W, D1) and (W0, D10) adjacent: one copy saves both
+constexpr int SC_FL_LOGP = 8, SC_FL_GMAX = 9;   // launch_flap_rows' two results, adjacent
+
+static double* flvec(sgp_ctx* c, int k) { return c->fl + (int64_t)k * c->n_pad; }
+
+static int flap_ensure(sgp_ctx* c) {
+  int st = lap_ensure(c);
+  if (st || c->fl) return st;
+  st = dalloc(&c->fl, FL_N * c->n_pad);
+  if (st) return st;
+  HIPCHK(hipMemset(c->fl, 0, sizeof(double) * FL_N * c->n_pad));
+  HIPCHK(hipDeviceSynchronize());   // null-stream memset before the context's streams use it
+  return SGP_OK;
+}
+
+// The state at the resident f (FL_RF current): row vectors, B^-1 in Binv, a in FL_A, and the
+// objective value read back with grad psi's maximum and the chains' status.
+static int flap_state(sgp_ctx* c, double* obj, double* gmax) {
+  const int64_t n = c->n, mp = c->mp;
+  hipStream_t s = c->stream;
+  {
+    Scope t(c, "flap_state");
+    HIPCHK(launch_flap_gemv(c->K22inv, mp, flvec(c, FL_RF), nullptr, nullptr, flvec(c, FL_Q), s));
+    HIPCHK(launch_flap_rows(n, c->n_pad, lvec(c, LV_F), c->y, c->mu, flvec(c, FL_Q), c->lap_expo,
+                            c->lap_av, c->lap_family, flvec(c, FL_W), flvec(c, FL_SW),
+                            flvec(c, FL_D1), flvec(c, FL_W3), flvec(c, FL_B), flvec(c, FL_GP),
+                            c->slab_small, c->slab_small_cap, c->sc + SC_FL_LOGP, s));
+    HIPCHK(launch_flap_scale(true, c->K22, flvec(c, FL_SW), c->Binv, mp, n, s));
+  }
+  {
+    Scope t(c, "flap_inverse");
+    HIPCHK(dense_spd_inverse(c->Binv, mp, c->Xt, c->dinv, c->logdB, c->status + 1, c->gjs, s));
+    HIPCHK(launch_sum_small(c->logdB, mp / SGP_DB, c->sc + SC_LDB, s));
+  }
+  {
+    Scope t(c, "flap_step");
+    HIPCHK(launch_flap_gemv(c->K22, mp, flvec(c, FL_B), flvec(c, FL_SW), nullptr,
+                            flvec(c, FL_T2), s));
+    HIPCHK(launch_flap_gemv(c->Binv, mp, flvec(c, FL_T2), flvec(c, FL_SW), flvec(c, FL_B),
+                            flvec(c, FL_A), s));
+    HIPCHK(launch_dot(flvec(c, FL_A), flvec(c, FL_RF), mp, c->slab_small, c->sc + SC_RR, s));
+  }
+  double sc[SC_N];
+  int status[4];
+  {
+    Readback rb(c);
+    HIPCHK(rb.add(sc, c->sc, sizeof(sc)));
+    HIPCHK(rb.add(status, c->status, sizeof(status)));
+    HIPCHK(rb.wait());
+  }
+  if (chain_watchdog(status)) return SGP_EHIP;
+  if (status[0] || status[1]) {
+    set_err("chol(): the leading minor of order %d of %s is not positive definite",
+            status[0] ? status[0] : status[1],
+            status[0] ? "Sigma" : "I + sqrt(-W) %*% Sigma %*% sqrt(-W)");
+    return SGP_ENOTPD;
+  }
+  // -(1/2) t(a) %*% (ff - mu) + log_py - sum(log(diag(L)))   (sc[SC_LDB] = 1/2 log det B)
+  *obj = -0.5 * sc[SC_RR] + sc[SC_FL_LOGP] - sc[SC_LDB];
+  *gmax = sc[SC_FL_GMAX];
+  if (!std::isfinite(*obj)) {
+    set_err("the full-GP Laplace objective is not finite (I + sqrt(-W) %%*%% Sigma %%*%% sqrt(-W) "
+            "holds non-finite values)");
+    return SGP_ENOTPD;
+  }
+  return SGP_OK;
+}
+
+int sgp_eval_full_laplace(sgp_ctx* c, int kernel, const double* theta, double delta, double expo,
+                          double tol, int maxit, unsigned flags, double* obj, double* grad,
+                          int* nr_iters) {
+  MULTI_REFUSE(c, "sgp_eval_full_laplace (the full GP needs every row on one device)");
+  if (!c) { set_err("context is NULL"); return SGP_EINVAL; }
+  const bool obj_only = (flags & SGP_FLAG_OBJ_ONLY) != 0;
+  if (!obj || (!grad && !obj_only)) { set_err("invalid arguments"); return SGP_EINVAL; }
+  if (kernel == SGP_KERNEL_EXP) {
+    set_err("fused evaluation supports 'sqexp' and 'ard' (optimize_gp.R:263 rejects others)");
+    return SGP_EINVAL;
+  }
+  if (c->n > c->m_max) {
+    set_err("the full GP needs m_max >= n (n = %lld, m_max = %lld)", (long long)c->n,
+            (long long)c->m_max);
+    return SGP_EINVAL;
+  }
+  if (!(expo >= 0.0) || !std::isfinite(expo) || !(tol >= 0.0) || maxit < 0) {
+    set_err("invalid Laplace controls (expo=%g, tol=%g, maxit=%d)", expo, tol, maxit);
+    return SGP_EINVAL;
+  }
+  if (expo == SGP_EXPO_ROWS && !c->lap_expo_rows) {
+    set_err("expo = SGP_EXPO_ROWS but no per-row exposure was set (sgp_lap_set_expo)");
+    return SGP_EINVAL;
+  }
+  KernParams kp;
+  int st = make_params(kernel, c->d, theta, delta, &kp);
+  if (st) return st;
+  if (!(kp.tau > 0.0) || !(kp.sigma > 0.0)) {
+    set_err("sigma and tau must be positive");
+    return SGP_EINVAL;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  st = drain_abandoned(c);   // before U is overwritten below
+  if (st) return st;
+  st = flap_ensure(c);
+  if (st) return st;
+  timers_reset(c);
+  c->kp = kp;
+  c->m = c->n;
+  c->mp = round_up(c->n, SGP_TILE);
+  c->delta = delta;
+  c->flags = flags;
+  c->phase = 0;
+  c->last_mode = 0;
+  c->knot_raw.clear();
+  c->lap_state = LS_NONE;
+  c->lap_expo = expo == SGP_EXPO_ROWS ? 1.0 : expo;
+  c->lap_av = expo == SGP_EXPO_ROWS ? lvec(c, LV_AEXP) : nullptr;
+  c->lap_tol = tol;
+  c->lap_maxit = maxit;
+  c->lap_it = 0;
+  c->lap_gpsi_valid = false;
+  c->fl_valid = false;
+  c->lap_objs.clear();
+  const int64_t n = c->n, n_pad = c->n_pad, mp = c->mp;
+  hipStream_t s = c->stream;
+  // the rows are the "knots": X (ld n_pad) -> U (ld mp), zero padded alike (mp == n_pad)
+  HIPCHK(hipMemcpy2DAsync(c->U, sizeof(double) * mp, c->X, sizeof(double) * n_pad,
+                          sizeof(double) * mp, (size_t)c->d, hipMemcpyDeviceToDevice, s));
+  c->knots_valid = false;
+  ++c->knots_gen;
+  HIPCHK(hipMemsetAsync(c->status, 0, sizeof(int) * 4, s));
+  HIPCHK(hipMemsetAsync(c->sc, 0, sizeof(double) * SC_N, s));
+  st = k22_stage(c, 0.0);   // Sigma (K22) and Sigma^-1 (K22inv): newtrapGP.R:43-56
+  if (st) return st;
+  HIPCHK(launch_flap_update(n, n_pad, nullptr, c->mu, lvec(c, LV_F), flvec(c, FL_RF), s));
+  HIPCHK(hipStreamWaitEvent(s, c->ev_k22, 0));
+  double o = 0.0, gmax = 0.0;
+  st = flap_state(c, &o, &gmax);   // obj_fun_vals[1] (newtrapGP.R:60)
+  if (st) return st;
+  c->lap_objs.push_back(o);
+  c->lap_it = 1;
+  // maxit = 0: objective and gradient at the resident f as given (the sparse path's convention);
+  // any maxit >= 1 runs the first update unconditionally, as newtrapGP.R:63-75 does
+  bool go = maxit > 0;
+  while (go) {
+    {
+      Scope t(c, "flap_step");
+      // newtrapGP returns W, grad_log_py_ff and grad_psi of the iterate this update starts from
+      HIPCHK(hipMemcpyAsync(flvec(c, FL_W0), flvec(c, FL_W), sizeof(double) * 2 * n_pad,
+                            hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipMemcpyAsync(lvec(c, LV_GPSI), flvec(c, FL_GP), sizeof(double) * n_pad,
+                            hipMemcpyDeviceToDevice, s));
+      HIPCHK(launch_flap_gemv(c->K22, mp, flvec(c, FL_A), nullptr, nullptr, flvec(c, FL_Y), s));
+      HIPCHK(launch_flap_update(n, n_pad, flvec(c, FL_Y), c->mu, lvec(c, LV_F),
+                                flvec(c, FL_RF), s));
+    }
+    c->lap_gpsi_valid = true;
+    c->fl_valid = true;
+    const double o_prev = o, g_start = gmax;
+    st = flap_state(c, &o, &gmax);
+    if (st) return st;
+    c->lap_objs.push_back(o);
+    c->lap_it += 1;
+    go = c->lap_it < maxit && (fabs(o - o_prev) > tol || g_start > tol);   // newtrapGP.R:77
+  }
+  c->lap_obj = o;
+  *obj = o;
+  if (nr_iters) *nr_iters = c->lap_it;
+  if (obj_only) return SGP_OK;
+  {
+    Scope t(c, "flap_grad");
+    HIPCHK(launch_flap_scale(false, c->Binv, flvec(c, FL_SW), c->Binv, mp, n, s));   // R
+    HIPCHK(launch_gemm64(false, false, false, mp, mp, mp, 1.0, c->K22, mp, c->Binv, mp, 0.0,
+                         c->T1, mp, s));                                              // Sigma R
+    HIPCHK(launch_flap_rowdot(c->K22, c->T1, mp, n, flvec(c, FL_W3), flvec(c, FL_S2), s));
+    HIPCHK(launch_flap_gemv(c->K22, mp, flvec(c, FL_S2), nullptr, nullptr, flvec(c, FL_TMP), s));
+    HIPCHK(launch_flap_gemv(c->Binv, mp, flvec(c, FL_TMP), nullptr, flvec(c, FL_S2),
+                            flvec(c, FL_V), s));                          // v = s2 - R Sigma s2
+    int nb = 0;
+    // b = 0: the (Ainv - Binv) operand is not used; R stands in for both
+    HIPCHK(launch_contract_kmm(kp, c->U, mp, c->m, mp, flvec(c, FL_A), c->Binv, c->Binv, c->Binv,
+                               0.5, 0.0, -0.5, flvec(c, FL_V), flvec(c, FL_D1), 0.5,
+                               c->slab_small, c->slab_small_cap, &nb, s));
+    HIPCHK(launch_colsum(c->slab_small, nb, kp.P, c->sc + SC_G22, s));
+  }
+  double sc[SC_N];
+  int status[4];
+  {
+    Readback rb(c);
+    HIPCHK(rb.add(sc, c->sc, sizeof(sc)));
+    HIPCHK(rb.add(status, c->status, sizeof(status)));
+    HIPCHK(rb.wait());
+  }
+  if (chain_watchdog(status)) return SGP_EHIP;
+  const double* g22 = sc + SC_G22;
+  grad[0] = g22[0];
+  for (int q = 0; q < kp.L; ++q) grad[1 + q] = g22[1 + q];
+  grad[kp.L + 1] = 2.0 * kp.tau2 * g22[kp.P - 1];   // tau: 2 tau^2 on coincident pairs (Q5)
+  return SGP_OK;
+}
+
+// newtrapGP's returned `W` and `grad_log_py_ff` (R/newtrapGP.R:96-99): the values at the iterate
+// the last update started from, which predict_laplace_full consumes
+int sgp_full_laplace_state(sgp_ctx* c, double* W, double* grad_log_py_ff) {
+  MULTI_REFUSE(c, "sgp_full_laplace_state");
+  if (!c || !W || !grad_log_py_ff) { set_err("invalid arguments"); return SGP_EINVAL; }
+  if (!c->fl_valid) {
+    set_err("no full-GP Laplace Newton-Raphson step has run since the mode was last set");
+    return SGP_EINVAL;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(W, flvec(c, FL_W0), sizeof(double) * c->n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(grad_log_py_ff, flvec(c, FL_D10), sizeof(double) * c->n,
+                   hipMemcpyDeviceToHost));
+  return SGP_OK;
+}
+
 // ------------------------------------------------------------------------- knot posterior
 // u | y at the end of the drivers, from the replicated state of the last evaluation:
 //   VI / FITC (vi_functions.R:1161-1180, laplace_gradient_ascent.R:1635-1655):
@@ -2723,7 +2962,11 @@ int sgp_predict(int device, int kernel, const double* theta, double delta, int m
     set_err("prediction supports 'sqexp' and 'ard' (optimize_gp.R:263 rejects others)");
     return SGP_EINVAL;
   }
-  const bool full = method == SGP_PRED_FULL;   // u_var unused (zero): Sigma22 = the data block
+  // predict_laplace_full (R/laplace_approx_prediction.R:128-214): U = xy, u_mean =
+  // grad_log_py_ff, muu = W of the newtrapGP fit
+  const bool lapfull = method == SGP_PRED_LAPLACE_FULL;
+  // u_var unused (zero): Sigma22 = the data block
+  const bool full = method == SGP_PRED_FULL || lapfull;
   if (!U || m < 1 || ldu < m || !u_mean || !muu || (!u_var && !full) || (!full && ldv < m) ||
       !x_pred || np < 1 ||
       ldxp < np || !mu_pred || !pred_mean || !pred_var || (full_cov && ldpv < np)) {
@@ -2735,10 +2978,16 @@ int sgp_predict(int device, int kernel, const double* theta, double delta, int m
     col_range(x_pred, np, ldxp, d, &plo, &phi);
     set_center(&kp, U, m, ldu, plo.data(), phi.data());
   }
-  if (method != SGP_PRED_VI && method != SGP_PRED_LAPLACE && method != SGP_PRED_FULL) {
+  if (method != SGP_PRED_VI && method != SGP_PRED_LAPLACE && method != SGP_PRED_FULL &&
+      !lapfull) {
     set_err("invalid prediction method %d", method);
     return SGP_EINVAL;
   }
+  for (int64_t j = 0; lapfull && j < m; ++j)
+    if (!(muu[j] <= 0.0)) {   // W = d2 log p(y|f) / df2 enters as sqrt(-W)
+      set_err("SGP_PRED_LAPLACE_FULL: W[%lld] = %g is not <= 0", (long long)j, muu[j]);
+      return SGP_EINVAL;
+    }
   if (method == SGP_PRED_VI && !gaussian) {
     set_err("Error: VI not supported for non-gaussian data.");   // predict_gp, l.424-427
     return SGP_EINVAL;
@@ -2779,7 +3028,13 @@ int sgp_predict(int device, int kernel, const double* theta, double delta, int m
       for (int64_t i = 0; i < np; ++i) hX[(size_t)(c * npp + i)] = x_pred[i + c * ldxp];
     }
     std::vector<double> hd((size_t)mp, 0.0), hV((size_t)mm, 0.0);
-    for (int64_t j = 0; j < m; ++j) hd[(size_t)j] = u_mean[j] - muu[j];
+    for (int64_t j = 0; j < m; ++j)
+      hd[(size_t)j] = lapfull ? sqrt(-muu[j]) : u_mean[j] - muu[j];   // lapfull: sqrt(-W)
+    if (lapfull) {
+      std::vector<double> hg((size_t)mp, 0.0);
+      for (int64_t j = 0; j < m; ++j) hg[(size_t)j] = u_mean[j];
+      HIPCHK(hipMemcpy(wv.p, hg.data(), sizeof(double) * mp, hipMemcpyHostToDevice));
+    }
     if (!full)
       for (int64_t i = 0; i < m; ++i)
         for (int64_t j = 0; j < m; ++j) hV[(size_t)(i * mp + j)] = u_var[i + j * ldv];
@@ -2797,16 +3052,26 @@ int sgp_predict(int device, int kernel, const double* theta, double delta, int m
   // (predict_gp_full, laplace_approx_prediction.R:281-405: Sigma22 = k(xy, xy) + (tau^2+delta) I)
   const double diag_sub = (gaussian && !full) ? kp.tau2 : 0.0;
   HIPCHK(launch_build_kmm(kp, dU.p, mp, m, mp, diag_sub, K22.p, s));
-  HIPCHK(hipMemcpyAsync(Kinv.p, K22.p, sizeof(double) * mm, hipMemcpyDeviceToDevice, s));
-  HIPCHK(dense_spd_inverse(Kinv.p, mp, R.p, Pb.p, logd.p, status.p,
-                           reinterpret_cast<unsigned*>(gsync.p), s));
-  HIPCHK(dense_gemv(Kinv.p, mp, wv.p + mp, 1.0, wv.p, s));          // Sigma22^-1 (u_mean - muu)
-  HIPCHK(launch_gemm64(false, false, false, mp, mp, mp, 1.0, Kinv.p, mp, V.p, mp, 0.0, T1.p, mp,
-                       s));
-  HIPCHK(launch_gemm64(false, false, false, mp, mp, mp, 1.0, T1.p, mp, Kinv.p, mp, 0.0, T22.p, mp,
-                       s));                                           // Sigma22^-1 u_var Sigma22^-1
   const bool lap_full = (method == SGP_PRED_LAPLACE) && full_cov;
-  if (!lap_full) HIPCHK(dense_axpby(1.0, T22.p, -1.0, Kinv.p, T22.p, mm, s));   // temp22
+  if (lapfull) {
+    // t(v) %*% v = Sigma12 R Sigma21 with R = sW (I + sW Sigma sW)^-1 sW (l.169, 188, 206):
+    // temp22 = -R; the mean's multiplier grad_log_py_ff is in wv already (l.209)
+    HIPCHK(launch_flap_scale(true, K22.p, wv.p + mp, Kinv.p, mp, m, s));
+    HIPCHK(dense_spd_inverse(Kinv.p, mp, R.p, Pb.p, logd.p, status.p,
+                             reinterpret_cast<unsigned*>(gsync.p), s));
+    HIPCHK(launch_flap_scale(false, Kinv.p, wv.p + mp, Kinv.p, mp, m, s));
+    HIPCHK(dense_axpby(0.0, V.p, -1.0, Kinv.p, T22.p, mm, s));   // V holds zeros
+  } else {
+    HIPCHK(hipMemcpyAsync(Kinv.p, K22.p, sizeof(double) * mm, hipMemcpyDeviceToDevice, s));
+    HIPCHK(dense_spd_inverse(Kinv.p, mp, R.p, Pb.p, logd.p, status.p,
+                             reinterpret_cast<unsigned*>(gsync.p), s));
+    HIPCHK(dense_gemv(Kinv.p, mp, wv.p + mp, 1.0, wv.p, s));        // Sigma22^-1 (u_mean - muu)
+    HIPCHK(launch_gemm64(false, false, false, mp, mp, mp, 1.0, Kinv.p, mp, V.p, mp, 0.0, T1.p, mp,
+                         s));
+    HIPCHK(launch_gemm64(false, false, false, mp, mp, mp, 1.0, T1.p, mp, Kinv.p, mp, 0.0, T22.p,
+                         mp, s));                                     // Sigma22^-1 u_var Sigma22^-1
+    if (!lap_full) HIPCHK(dense_axpby(1.0, T22.p, -1.0, Kinv.p, T22.p, mm, s));   // temp22
+  }
   HIPCHK(launch_build_knm(kp, Xp.p, npp, np, npp, dU.p, mp, m, mp, Kp.p, s));
   HIPCHK(launch_gemv_rows(Kp.p, npp, mp, wv.p, nullptr, yv.p, nullptr, s));
   std::vector<double> hy((size_t)npp), hq((size_t)npp, 0.0);
@@ -2832,7 +3097,8 @@ int sgp_predict(int device, int kernel, const double* theta, double delta, int m
   HIPCHK(hipMemcpyAsync(hst, status.p, sizeof(hst), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (hst[0]) {
-    set_err("Sigma22 is not positive definite (leading minor of order %d)", hst[0]);
+    set_err("%s is not positive definite (leading minor of order %d)",
+            lapfull ? "I + sqrt(-W) %*% Sigma %*% sqrt(-W)" : "Sigma22", hst[0]);
     return SGP_ENOTPD;
   }
   for (int64_t i = 0; i < np; ++i) pred_mean[i] = mu_pred[i] + hy[(size_t)i];

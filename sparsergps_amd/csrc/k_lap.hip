@@ -333,6 +333,201 @@ __global__ void __launch_bounds__(256) k_gemv_rows(const double* __restrict__ K,
   }
 }
 
+// ------------------------------------------------------------------ full-GP Laplace
+// newtrapGP (R/newtrapGP.R:6-177), obj_fun_pois_full / obj_fun_bern_full
+// (R/laplace_approx_obj_funs.R:67-102, 346-397) and dlogq_dcov_par_full
+// (R/laplace_approx_gradient.R:558-711) over Sigma = k(xy, xy) + (tau^2 + delta) I.  The n x n
+// matrices are mp x mp row-major with mp = n_pad; every access below is 16 bytes per lane.
+
+// Row state at f: W, sW = sqrt(-W), d1 = d log p / df, W3, b = -W (f - mu) + d1
+// (newtrapGP.R:166) and grad psi = d1 - q with q = Sigma^-1 (f - mu) given
+// (grad_loglik_fn_pois_full / _bern_full, derivative_functions_of_data_likelihoods.R:65-84,
+// 239-267).  Rows i >= n get exact zeros in every vector (a padded Poisson row would otherwise
+// carry d1 = -a into the matrix-vector products).  slab[2 blk] = sum log p(y_i | f_i),
+// slab[2 blk + 1] = max |grad psi_i| of the block's rows.
+template <int FAM>
+__global__ void __launch_bounds__(256) k_flap_rows(int64_t n, int64_t n_pad,
+                                                   const double* __restrict__ f,
+                                                   const double* __restrict__ y,
+                                                   const double* __restrict__ mu,
+                                                   const double* __restrict__ q, double expo,
+                                                   double logexpo, const double* __restrict__ av,
+                                                   double* __restrict__ W, double* __restrict__ sW,
+                                                   double* __restrict__ d1, double* __restrict__ W3,
+                                                   double* __restrict__ b,
+                                                   double* __restrict__ gpsi,
+                                                   double* __restrict__ slab) {
+  __shared__ double sh[2][4];
+  double lp = 0.0, gm = 0.0;
+  const int64_t h = n_pad / 2;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < h; p += (int64_t)gridDim.x * 256) {
+    const double2 f2 = reinterpret_cast<const double2*>(f)[p];
+    const double2 y2 = reinterpret_cast<const double2*>(y)[p];
+    const double2 m2 = reinterpret_cast<const double2*>(mu)[p];
+    const double2 q2 = reinterpret_cast<const double2*>(q)[p];
+    const double fv[2] = {f2.x, f2.y}, yv[2] = {y2.x, y2.y}, mv[2] = {m2.x, m2.y},
+                 qv[2] = {q2.x, q2.y};
+    double w[2], s[2], g[2], w3[2], bv[2], gp[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int64_t i = 2 * p + k;
+      if (i < n) {
+        const double ai = LapLik<FAM>::expo(av, i, expo);
+        const double lai = LapLik<FAM>::logexpo(av, ai, logexpo);
+        const LapLik<FAM> lik(fv[k], yv[k], ai);
+        w[k] = lik.W();
+        w3[k] = lik.W3();
+        g[k] = lik.d1(yv[k]);
+        s[k] = sqrt(-w[k]);
+        bv[k] = -w[k] * (fv[k] - mv[k]) + g[k];
+        gp[k] = g[k] - qv[k];
+        lp += lik.logp(fv[k], yv[k], lai);
+        gm = fmax(gm, fabs(gp[k]));
+      } else {
+        w[k] = s[k] = g[k] = w3[k] = bv[k] = gp[k] = 0.0;
+      }
+    }
+    reinterpret_cast<double2*>(W)[p] = double2{w[0], w[1]};
+    reinterpret_cast<double2*>(sW)[p] = double2{s[0], s[1]};
+    reinterpret_cast<double2*>(d1)[p] = double2{g[0], g[1]};
+    reinterpret_cast<double2*>(W3)[p] = double2{w3[0], w3[1]};
+    reinterpret_cast<double2*>(b)[p] = double2{bv[0], bv[1]};
+    reinterpret_cast<double2*>(gpsi)[p] = double2{gp[0], gp[1]};
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  lp = wave_sum(lp);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) gm = fmax(gm, __shfl_xor(gm, o, 64));
+  if (lane == 0) {
+    sh[0][wv] = lp;
+    sh[1][wv] = gm;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    slab[2 * (int64_t)blockIdx.x] = ((sh[0][0] + sh[0][1]) + sh[0][2]) + sh[0][3];
+    slab[2 * (int64_t)blockIdx.x + 1] = fmax(fmax(sh[1][0], sh[1][1]), fmax(sh[1][2], sh[1][3]));
+  }
+}
+
+// out[0] = sum of the blocks' log p partials (block order), out[1] = max of their maxima
+__global__ void __launch_bounds__(256) k_flap_reduce(const double* __restrict__ slab, int nb,
+                                                     double* __restrict__ out) {
+  __shared__ double sh[2][4];
+  double lp = 0.0, gm = 0.0;
+  for (int e = threadIdx.x; e < nb; e += 256) {
+    lp += slab[2 * e];
+    gm = fmax(gm, slab[2 * e + 1]);
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  lp = wave_sum(lp);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) gm = fmax(gm, __shfl_xor(gm, o, 64));
+  if (lane == 0) {
+    sh[0][wv] = lp;
+    sh[1][wv] = gm;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    out[0] = ((sh[0][0] + sh[0][1]) + sh[0][2]) + sh[0][3];
+    out[1] = fmax(fmax(sh[1][0], sh[1][1]), fmax(sh[1][2], sh[1][3]));
+  }
+}
+
+// f = t + mu when t is given (the Newton step f <- Sigma a + mu, newtrapGP.R:172), then
+// rf = f - mu; rows i >= n: f untouched, rf = 0.
+__global__ void __launch_bounds__(256) k_flap_update(int64_t n, int64_t n_pad,
+                                                     const double* __restrict__ t,
+                                                     const double* __restrict__ mu,
+                                                     double* __restrict__ f,
+                                                     double* __restrict__ rf) {
+  const int64_t h = n_pad / 2;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < h; p += (int64_t)gridDim.x * 256) {
+    const double2 m2 = reinterpret_cast<const double2*>(mu)[p];
+    double2 f2 = reinterpret_cast<const double2*>(f)[p];
+    const bool v0 = 2 * p < n, v1 = 2 * p + 1 < n;
+    if (t) {
+      const double2 t2 = reinterpret_cast<const double2*>(t)[p];
+      if (v0) f2.x = t2.x + m2.x;
+      if (v1) f2.y = t2.y + m2.y;
+      reinterpret_cast<double2*>(f)[p] = f2;
+    }
+    reinterpret_cast<double2*>(rf)[p] = double2{v0 ? f2.x - m2.x : 0.0, v1 ? f2.y - m2.y : 0.0};
+  }
+}
+
+// FWD: out = I + diag(sW) A diag(sW) (B of newtrapGP.R:163, identity outside the n x n block);
+// else out = diag(sW) A diag(sW) (R of laplace_approx_gradient.R:624-625 from A = B^-1, zero
+// outside).  One row per blockIdx.y; out may be A.
+template <bool FWD>
+__global__ void __launch_bounds__(256) k_flap_scale(const double* A, const double* __restrict__ sW,
+                                                    double* out, int64_t mp, int64_t n) {
+  const int64_t i = blockIdx.y;
+  const int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
+  if (j >= mp) return;
+  double2 v = double2{0.0, 0.0};
+  if (i < n) {
+    const double2 a = *reinterpret_cast<const double2*>(A + i * mp + j);
+    const double2 s = *reinterpret_cast<const double2*>(sW + j);
+    const double si = sW[i];
+    v.x = j < n ? si * a.x * s.x : 0.0;
+    v.y = j + 1 < n ? si * a.y * s.y : 0.0;
+  }
+  if (FWD) {
+    if (j == i) v.x += 1.0;
+    if (j + 1 == i) v.y += 1.0;
+  }
+  *reinterpret_cast<double2*>(out + i * mp + j) = v;
+}
+
+// y_i = sub_i - rs_i (A x)_i when sub is given, else rs_i (A x)_i (rs == nullptr: 1); one wave
+// per row, fixed summation order.
+__global__ void __launch_bounds__(256) k_flap_gemv(const double* __restrict__ A, int64_t mp,
+                                                   const double* __restrict__ x,
+                                                   const double* __restrict__ rs,
+                                                   const double* __restrict__ sub,
+                                                   double* __restrict__ y) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= mp) return;
+  const double2* row = reinterpret_cast<const double2*>(A + i * mp);
+  const double2* X = reinterpret_cast<const double2*>(x);
+  double s = 0.0;
+  for (int64_t c = lane; c < mp / 2; c += 64) {
+    const double2 k = row[c];
+    const double2 a = X[c];
+    s = fma(k.x, a.x, s);
+    s = fma(k.y, a.y, s);
+  }
+  s = wave_sum(s);
+  if (lane == 0) {
+    const double r = rs ? rs[i] * s : s;
+    y[i] = sub ? sub[i] - r : r;
+  }
+}
+
+// s2_i = -1/2 (Sigma_ii - sum_j T_ij Sigma_ij) (-W3_i) with T = Sigma R, i.e.
+// -1/2 diag(diag(Sigma11) - diag(C^T C)) (-W3) of laplace_approx_gradient.R:631-633 (C^T C =
+// Sigma R Sigma); rows i >= n: 0.  One wave per row.
+__global__ void __launch_bounds__(256) k_flap_rowdot(const double* __restrict__ S,
+                                                     const double* __restrict__ T, int64_t mp,
+                                                     int64_t n, const double* __restrict__ W3,
+                                                     double* __restrict__ s2) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= mp) return;
+  const double2* sr = reinterpret_cast<const double2*>(S + i * mp);
+  const double2* tr = reinterpret_cast<const double2*>(T + i * mp);
+  double s = 0.0;
+  for (int64_t c = lane; c < mp / 2; c += 64) {
+    const double2 a = sr[c];
+    const double2 b = tr[c];
+    s = fma(a.x, b.x, s);
+    s = fma(a.y, b.y, s);
+  }
+  s = wave_sum(s);
+  if (lane == 0) s2[i] = i < n ? (-0.5 * (S[i * mp + i] - s)) * (-W3[i]) : 0.0;
+}
+
 // part[ch][v][j] = sum_{i in chunk ch} K_ij V_v[i]  for v < NV (V_v = V + v * ldv)
 template <int NV>
 __global__ void __launch_bounds__(128) k_gemv_cols(const double* __restrict__ K, int64_t n_pad,
@@ -764,6 +959,62 @@ hipError_t launch_lap_grad_b(int64_t n, int64_t n_pad, const double* B, const do
   *nblocks = nb;
   hipLaunchKernelGGL(k_lap_grad_b, dim3(nb), dim3(256), 0, s, n, n_pad, B, sv, y3, dMt, c2, g, h,
                      a, slab);
+  return hipGetLastError();
+}
+
+hipError_t launch_flap_rows(int64_t n, int64_t n_pad, const double* f, const double* y,
+                            const double* mu, const double* q, double expo, const double* av,
+                            int fam, double* W, double* sW, double* d1, double* W3, double* b,
+                            double* gpsi, double* slab, int64_t slab_cap, double* out,
+                            hipStream_t s) {
+  int64_t nb = (n_pad / 2 + 255) / 256;
+  if (nb > 1024) nb = 1024;
+  if (2 * nb > slab_cap || n_pad % 2 != 0) return hipErrorInvalidValue;
+  if (fam == SGP_FAM_BERNOULLI)
+    hipLaunchKernelGGL(k_flap_rows<SGP_FAM_BERNOULLI>, dim3((unsigned)nb), dim3(256), 0, s, n,
+                       n_pad, f, y, mu, q, 1.0, 0.0, nullptr, W, sW, d1, W3, b, gpsi, slab);
+  else
+    hipLaunchKernelGGL(k_flap_rows<SGP_FAM_POISSON>, dim3((unsigned)nb), dim3(256), 0, s, n, n_pad,
+                       f, y, mu, q, expo, av ? 0.0 : log(expo), av, W, sW, d1, W3, b, gpsi, slab);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_flap_reduce, dim3(1), dim3(256), 0, s, slab, (int)nb, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_flap_update(int64_t n, int64_t n_pad, const double* t, const double* mu,
+                              double* f, double* rf, hipStream_t s) {
+  int64_t nb = (n_pad / 2 + 255) / 256;
+  if (nb > 1024) nb = 1024;
+  if (n_pad % 2 != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_flap_update, dim3((unsigned)nb), dim3(256), 0, s, n, n_pad, t, mu, f, rf);
+  return hipGetLastError();
+}
+
+hipError_t launch_flap_scale(bool forward, const double* A, const double* sW, double* out,
+                             int64_t mp, int64_t n, hipStream_t s) {
+  if (mp % 2 != 0 || mp > 65535 || n > mp) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((mp / 2 + 255) / 256), (unsigned)mp);
+  if (forward)
+    hipLaunchKernelGGL(k_flap_scale<true>, grid, dim3(256), 0, s, A, sW, out, mp, n);
+  else
+    hipLaunchKernelGGL(k_flap_scale<false>, grid, dim3(256), 0, s, A, sW, out, mp, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_flap_gemv(const double* A, int64_t mp, const double* x, const double* rs,
+                            const double* sub, double* y, hipStream_t s) {
+  if (mp % 2 != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_flap_gemv, dim3((unsigned)((mp + 3) / 4)), dim3(256), 0, s, A, mp, x, rs,
+                     sub, y);
+  return hipGetLastError();
+}
+
+hipError_t launch_flap_rowdot(const double* S, const double* T, int64_t mp, int64_t n,
+                              const double* W3, double* s2, hipStream_t s) {
+  if (mp % 2 != 0 || n > mp) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_flap_rowdot, dim3((unsigned)((mp + 3) / 4)), dim3(256), 0, s, S, T, mp, n,
+                     W3, s2);
   return hipGetLastError();
 }
 

@@ -392,6 +392,29 @@ hipError_t launch_lap_grad_b(int64_t n, int64_t n_pad, const double* B, const do
                              const double* g, double* h, double* a, double* slab, int* nblocks,
                              hipStream_t s);
 
+// Full-GP Laplace (newtrapGP + dlogq_dcov_par_full; k_lap.hip).  Vectors hold n_pad = mp values,
+// matrices are mp x mp row-major.
+// Row state at f with q = Sigma^-1 (f - mu): W, sW, d1, W3, b = -W (f - mu) + d1, gpsi = d1 - q
+// (zeros for rows >= n); out[0] = sum log p(y_i | f_i), out[1] = max |gpsi_i|.  slab: 2048 doubles.
+hipError_t launch_flap_rows(int64_t n, int64_t n_pad, const double* f, const double* y,
+                            const double* mu, const double* q, double expo, const double* av,
+                            int fam, double* W, double* sW, double* d1, double* W3, double* b,
+                            double* gpsi, double* slab, int64_t slab_cap, double* out,
+                            hipStream_t s);
+// f = t + mu (t != nullptr), then rf = f - mu (0 for rows >= n)
+hipError_t launch_flap_update(int64_t n, int64_t n_pad, const double* t, const double* mu,
+                              double* f, double* rf, hipStream_t s);
+// forward: out = I + diag(sW) A diag(sW), identity padded; else out = diag(sW) A diag(sW), zero
+// padded.  out may be A.
+hipError_t launch_flap_scale(bool forward, const double* A, const double* sW, double* out,
+                             int64_t mp, int64_t n, hipStream_t s);
+// y = sub - rs o (A x) (sub given) or rs o (A x); rs == nullptr: ones
+hipError_t launch_flap_gemv(const double* A, int64_t mp, const double* x, const double* rs,
+                            const double* sub, double* y, hipStream_t s);
+// s2_i = 1/2 (S_ii - sum_j T_ij S_ij) W3_i for i < n, else 0
+hipError_t launch_flap_rowdot(const double* S, const double* T, int64_t mp, int64_t n,
+                              const double* W3, double* s2, hipStream_t s);
+
 // knot gradients (k_mfma.hip / k_cov.hip)
 // out[j*d + c] (+)= sum over row tiles of knot_slab (deterministic two-level reduction);
 // part: 64 * mp * d doubles of work space

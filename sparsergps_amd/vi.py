@@ -308,6 +308,30 @@ class SparseGPContext:
                                               _lib.dptr(grad), C.byref(it)))
         return obj.value, grad, it.value
 
+    def eval_full_laplace(self, theta, cov_fun, delta=1e-6, expo=1.0, tol=1e-6, maxit=1000,
+                          obj_only=False):
+        """Full-GP Laplace over this context's rows (m_max >= n): newtrapGP from the resident f
+        (R/newtrapGP.R:6-177), then dlogq_dcov_par_full at the mode
+        (R/laplace_approx_gradient.R:558-711): (log q(y | theta, f_hat), d/d log(theta) or None
+        with obj_only, length(objective_function_values))."""
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        obj = C.c_double(0.0)
+        it = C.c_int(0)
+        grad = None if obj_only else np.zeros(theta.size, dtype=np.float64)
+        _lib.check(self._lib.sgp_eval_full_laplace(
+            self.handle, _lib.KERNELS[cov_fun], _lib.dptr(theta), float(delta), self._expo(expo),
+            float(tol), int(maxit), self._flags(False, obj_only), C.byref(obj),
+            None if grad is None else _lib.dptr(grad), C.byref(it)))
+        return obj.value, grad, it.value
+
+    def full_laplace_state(self):
+        """newtrapGP's returned (W, grad_log_py_ff) of the last full-GP Laplace NR run: the values
+        at the iterate its last update started from (R/newtrapGP.R:96-99)."""
+        W = np.zeros(self.n, dtype=np.float64)
+        g = np.zeros(self.n, dtype=np.float64)
+        _lib.check(self._lib.sgp_full_laplace_state(self.handle, _lib.dptr(W), _lib.dptr(g)))
+        return W, g
+
     def vi_candidates(self, theta, cov_fun, xu, cand, delta=1e-6, r_det=False):
         """ELBO at knots [xu; cand[t]] for every candidate row t (OAT proposal scoring)."""
         theta = np.ascontiguousarray(theta, dtype=np.float64)
