@@ -142,6 +142,26 @@ __device__ __forceinline__ void mfma_interleave() {
 // ms), but the same pin made the VI SYRK 10 % and the contraction 1.5 % slower and the omega
 // SYRK 5 % slower (profiles/r3/gload_pin_ab.txt), so only the t variants use it.
 
+// Issue order of a ring sub-step (con_tile's RING has the schedule) as mfma_interleave's request:
+// NMFMA MFMAs; the NVMEM global loads of sub-stage j + 3 behind the first ones; the second
+// k-slice's fragment reads of sub-stage j with them (NRD instructions per slice); the first
+// slice of j + 1 from the middle of the sub-step, into the registers the current first slice
+// has just left; the NWR stores of j + 2 late, four MFMAs before the barrier.
+constexpr int SYRK_RING_HS = (BK / 2) * SB;   // a sub-stage of the SYRK rings' [k][128] images
+template <int NRD, int NWR, int NMFMA = 32, int NVMEM = 4>
+__device__ __forceinline__ void ring_interleave() {
+#pragma unroll
+  for (int i = 0; i < NMFMA; ++i) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                      // MFMA
+    if (i < NVMEM) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);       // VMEM read
+    if (i < NRD) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);         // DS read, slice 1
+    if (i >= NMFMA / 2 && i < NMFMA / 2 + NRD)
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                    // DS read, next slice 0
+    constexpr int w0 = NMFMA - 4 - NWR;
+    if (i >= w0 && i < w0 + NWR) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // DS write
+  }
+}
+
 // Balanced plan (syrk_plan_bal): a diagonal 128-tile t of S -- 36 lower 16x16 fragments -- split
 // over the 4 waves of one workgroup as fragment rows v and 7 - v (9 fragments each: 36 MFMAs per
 // step, not the 64 of a packed 64-block wave); these workgroups take longer row chunks so that
@@ -202,6 +222,80 @@ __device__ __forceinline__ void syrk_dt_body(const double* __restrict__ K, int64
       rrp = fma(rw_ * (fold), vrr, rrp);                                        \
     }                                                                           \
   }
+  if constexpr (COMPACT && WMODE == 0 && TMODE == 0 && SGP_SYRK_RING != 0) {
+    // The work-balanced plan's runs (k_syrk_bal; nsteps >= 1) as syrk_off_seg's ring: the image
+    // as four 8-deep sub-stages, 18 MFMAs per sub-step, the same MFMAs in the same order per
+    // accumulator.
+    double* Rk = &Ka[0][0];
+    const int rrow = tid >> 5, rc = tid & 31;
+    const double2* rA = reinterpret_cast<const double2*>(K + (rbeg + rrow) * mp + t * (int64_t)T128) + rc;
+    const int64_t rsub = (BK / 2) * mp / 2;
+    const int nsub = 2 * nsteps;
+    double2 p0, p1, q0, q1;   // staging sets of the even and of the odd sub-stages
+    double s0[N1];            // first k-slice of the current sub-stage: fragments 0 .. R1
+    int fo[4][2];
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int sl = 0; sl < 2; ++sl) {
+        fo[b][sl] = b * SYRK_RING_HS + (sl * 4 + (lane >> 4)) * SB + (lane & 15);
+        asm volatile("" : "+v"(fo[b][sl]));
+      }
+#define RING_LOAD(sub_, A0, A1)                                                 \
+  {                                                                             \
+    const int s_ = (sub_) < nsub ? (sub_) : nsub - 1;   /* one basic block */   \
+    A0 = rA[(int64_t)s_ * rsub]; A1 = rA[(int64_t)s_ * rsub + 32];              \
+  }
+#define RING_STORE(buf_, A0, A1)                                                \
+  {                                                                             \
+    double2* p_ = reinterpret_cast<double2*>(Rk + (buf_) * SYRK_RING_HS + rrow * SB) + rc; \
+    p_[0] = A0; p_[32] = A1;                                                    \
+  }
+#define RING_READ(buf_, sl_, F)                                                 \
+  _Pragma("unroll") for (int c = 0; c < N1; ++c) F[c] = Rk[fo[buf_][sl_] + c * 16];
+#define RING_MFMA(F)                                                            \
+  _Pragma("unroll") for (int c = 0; c < N1; ++c) {                              \
+    if (c < N0) acc0[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(F[R0], F[c], acc0[c], 0, 0, 0); \
+    acc1[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(F[R1], F[c], acc1[c], 0, 0, 0); \
+  }
+#define RING_SUB(j_, R_, L0, L1, S0, S1)                                        \
+  {                                                                             \
+    RING_LOAD((j_) + 3, L0, L1);                                                \
+    double s1_[N1], n0_[N1];                                                    \
+    RING_READ(R_, 1, s1_);                                                      \
+    RING_MFMA(s0);                                                              \
+    RING_READ(((R_) + 1) & 3, 0, n0_);                                          \
+    RING_MFMA(s1_);                                                             \
+    RING_STORE(((R_) + 2) & 3, S0, S1);                                         \
+    ring_interleave<4, 2, 18, 2>();                                             \
+    __syncthreads();                                                            \
+    __builtin_amdgcn_sched_barrier(0);                                          \
+    _Pragma("unroll") for (int c = 0; c < N1; ++c) s0[c] = n0_[c];              \
+  }
+    RING_LOAD(0, p0, p1);
+    RING_LOAD(1, q0, q1);
+    RING_STORE(0, p0, p1);
+    RING_STORE(1, q0, q1);
+    RING_LOAD(2, p0, p1);
+    __syncthreads();
+    RING_READ(0, 0, s0);
+    int j = 0;
+    for (; j + 4 <= nsub; j += 4) {
+      RING_SUB(j, 0, q0, q1, p0, p1);
+      RING_SUB(j + 1, 1, p0, p1, q0, q1);
+      RING_SUB(j + 2, 2, q0, q1, p0, p1);
+      RING_SUB(j + 3, 3, p0, p1, q0, q1);
+    }
+    if (j < nsub) {   // an odd step count (uniform over the workgroup)
+      RING_SUB(j, 0, q0, q1, p0, p1);
+      RING_SUB(j + 1, 1, p0, p1, q0, q1);
+    }
+#undef RING_SUB
+#undef RING_MFMA
+#undef RING_READ
+#undef RING_STORE
+#undef RING_LOAD
+  } else {
   if (nsteps > 0) {
     SDT_GLOAD(0);
     SDT_SSTORE(0, 1.0);
@@ -241,6 +335,7 @@ __device__ __forceinline__ void syrk_dt_body(const double* __restrict__ K, int64
     if constexpr (SGP_SDT_IL && WMODE != 1) mfma_interleave<false, 2, 4, 36>();
     __syncthreads();
   }
+  }   // two-stage loop
 #undef SDT_GLOAD
 #undef SDT_SSTORE
   tacc = (t4[0] + t4[1]) + (t4[2] + t4[3]);
@@ -541,10 +636,10 @@ k_syrk_blk(const double* __restrict__ K, int64_t n_pad, int64_t mp, const double
 // sgp_syrk_plan.h deals the strictly-lower 128-tile groups in row bands and the diagonal tiles'
 // rows as filler so that every workgroup of the round carries the same modelled MFMA count; a
 // workgroup finds its (at most two) segments with the planner's own syrk_bp_segments.
-//
-// One band chunk of a strictly-lower group: k_syrk_blk<0, 0>'s step (the same operand staging,
-// fragment order and interleave request), wave (wr, wc) = the 64-block (2a + wr, 2b + wc) with
-// rows from image A (K panel a) and columns from image B (panel b); out: the group's 4 blocks.
+
+// One band chunk of a strictly-lower group: k_syrk_blk<0, 0>'s operands and fragment order (with
+// SGP_SYRK_RING 0 its step too), wave (wr, wc) = the 64-block (2a + wr, 2b + wc) with rows from
+// image A (K panel a) and columns from image B (panel b); out: the group's 4 blocks.
 __device__ __forceinline__ void syrk_off_seg(const double* __restrict__ K, int64_t mp, int ta,
                                              int tb, int64_t rbeg, int nsteps,
                                              double (*Ka)[BK * SB], double (*Kb)[BK * SB],
@@ -574,6 +669,95 @@ __device__ __forceinline__ void syrk_off_seg(const double* __restrict__ K, int64
     pa_[0] = va0; pa_[16] = va1; pa_[32] = va2; pa_[48] = va3;                  \
     pb_[0] = vb0; pb_[16] = vb1; pb_[32] = vb2; pb_[48] = vb3;                  \
   }
+  if constexpr (SGP_SYRK_RING) {
+    // The ring form of the k-loop (con_tile's RING has the schedule): the two 16-deep stages
+    // of each image as four 8-deep sub-stages, the first fragments of sub-stage j + 1 read
+    // during sub-step j.  The same MFMAs in the same order per accumulator.  nsteps is any
+    // count >= 1: whole groups of four sub-steps, then two more when it is odd.
+    constexpr int HS = SYRK_RING_HS;
+    double* Ra = &Ka[0][0];
+    double* Rb = &Kb[0][0];
+    const int rrow = tid >> 5, rc = tid & 31;   // 8 rows x 64 double2 per image and sub-stage
+    const double2* rA = reinterpret_cast<const double2*>(K + (rbeg + rrow) * mp + ta * (int64_t)T128) + rc;
+    const double2* rB = reinterpret_cast<const double2*>(K + (rbeg + rrow) * mp + tb * (int64_t)T128) + rc;
+    const int64_t rsub = (BK / 2) * mp / 2;
+    const int nsub = 2 * nsteps;
+    double2 pa0, pa1, pb0, pb1;   // staging set of the even sub-stages
+    double2 qa0, qa1, qb0, qb1;   // and of the odd ones
+    double a0[4], b0[4];          // first k-slice of the current sub-stage
+#define RING_LOAD(sub_, A0, A1, B0, B1)                                         \
+  {                                                                             \
+    const int s_ = (sub_) < nsub ? (sub_) : nsub - 1;   /* one basic block */   \
+    const int64_t o_ = (int64_t)s_ * rsub;                                      \
+    A0 = rA[o_]; A1 = rA[o_ + 32]; B0 = rB[o_]; B1 = rB[o_ + 32];               \
+  }
+#define RING_STORE(buf_, A0, A1, B0, B1)                                        \
+  {                                                                             \
+    double2* pa_ = reinterpret_cast<double2*>(Ra + (buf_) * HS + rrow * SB) + rc; \
+    double2* pb_ = reinterpret_cast<double2*>(Rb + (buf_) * HS + rrow * SB) + rc; \
+    pa_[0] = A0; pa_[32] = A1; pb_[0] = B0; pb_[32] = B1;                       \
+  }
+    // a lane's fragment offsets per (sub-stage, k-slice), each its own address register (an
+    // opaque move): left to itself hipcc derives some of them from others with offsets past
+    // ds_read2_b64's reach and issues those fragment reads singly, or pairs reads of two
+    // sub-stages (a multiple of 512 bytes apart) into one ds_read2st64_b64, and the issue
+    // order asked for below is lost
+    int fo[4][2];
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int sl = 0; sl < 2; ++sl) {
+        fo[b][sl] = b * HS + (sl * 4 + (lane >> 4)) * SB + (lane & 15);
+        asm volatile("" : "+v"(fo[b][sl]));
+      }
+#define RING_READ(buf_, sl_, AF, BF)                                            \
+  _Pragma("unroll") for (int f = 0; f < 4; ++f) {                               \
+    AF[f] = Ra[fo[buf_][sl_] + ro + f * 16];                                    \
+    BF[f] = Rb[fo[buf_][sl_] + co + f * 16];                                    \
+  }
+#define RING_MFMA(AF, BF)                                                       \
+  _Pragma("unroll") for (int fm = 0; fm < 4; ++fm)                              \
+    _Pragma("unroll") for (int fn = 0; fn < 4; ++fn)                            \
+      acc[fm][fn] = __builtin_amdgcn_mfma_f64_16x16x4f64(AF[fm], BF[fn], acc[fm][fn], 0, 0, 0);
+    // sub-step j_ (j_ % 4 == R_): loads j_ + 3 into L, stores j_ + 2 from S
+#define RING_SUB(j_, R_, L0, L1, L2, L3, S0, S1, S2, S3)                        \
+  {                                                                             \
+    RING_LOAD((j_) + 3, L0, L1, L2, L3);                                        \
+    double a1_[4], b1_[4], na_[4], nb_[4];                                      \
+    RING_READ(R_, 1, a1_, b1_);                                                 \
+    RING_MFMA(a0, b0);                                                          \
+    RING_READ(((R_) + 1) & 3, 0, na_, nb_);                                     \
+    RING_MFMA(a1_, b1_);                                                        \
+    RING_STORE(((R_) + 2) & 3, S0, S1, S2, S3);                                 \
+    ring_interleave<4, 4>();                                                    \
+    __syncthreads();                                                            \
+    __builtin_amdgcn_sched_barrier(0);                                          \
+    _Pragma("unroll") for (int f = 0; f < 4; ++f) { a0[f] = na_[f]; b0[f] = nb_[f]; } \
+  }
+    RING_LOAD(0, pa0, pa1, pb0, pb1);
+    RING_LOAD(1, qa0, qa1, qb0, qb1);
+    RING_STORE(0, pa0, pa1, pb0, pb1);
+    RING_STORE(1, qa0, qa1, qb0, qb1);
+    RING_LOAD(2, pa0, pa1, pb0, pb1);
+    __syncthreads();
+    RING_READ(0, 0, a0, b0);
+    int j = 0;
+    for (; j + 4 <= nsub; j += 4) {
+      RING_SUB(j, 0, qa0, qa1, qb0, qb1, pa0, pa1, pb0, pb1);
+      RING_SUB(j + 1, 1, pa0, pa1, pb0, pb1, qa0, qa1, qb0, qb1);
+      RING_SUB(j + 2, 2, qa0, qa1, qb0, qb1, pa0, pa1, pb0, pb1);
+      RING_SUB(j + 3, 3, pa0, pa1, pb0, pb1, qa0, qa1, qb0, qb1);
+    }
+    if (j < nsub) {   // an odd step count (uniform over the workgroup)
+      RING_SUB(j, 0, qa0, qa1, qb0, qb1, pa0, pa1, pb0, pb1);
+      RING_SUB(j + 1, 1, pa0, pa1, pb0, pb1, qa0, qa1, qb0, qb1);
+    }
+#undef RING_SUB
+#undef RING_MFMA
+#undef RING_READ
+#undef RING_STORE
+#undef RING_LOAD
+  } else {
   SYRKO_GLOAD(0);
   SYRKO_SSTORE(0);
   __syncthreads();
@@ -604,6 +788,7 @@ __device__ __forceinline__ void syrk_off_seg(const double* __restrict__ K, int64
     mfma_interleave<false, SGP_SYRK_IL_PAT, 8>();
     __syncthreads();
   }
+  }   // !SGP_SYRK_RING
 #undef SYRKO_GLOAD
 #undef SYRKO_SSTORE
   double* blk = out + (int64_t)wv * 4096;   // local block (wr, wc) = wv
@@ -1136,6 +1321,24 @@ constexpr int CON_A_SZ = T128 * SA;   // 2176 (keeps the B image 16-byte aligned
 constexpr int CON_B_SZ = BK * SB;     // 2304
 constexpr int CON_LDS = 2 * (CON_A_SZ + CON_B_SZ);
 
+// The ring form of the k-loop (con_tile's RING): the same LDS as four 8-deep sub-stages, A
+// [128][SA8] then B [8][SB] each.  SA8 odd: the 16 rows of an A-fragment read (ds_read2_b64,
+// banked per 16 lanes mod 32 dwords) and of a staging store (16 consecutive lanes = 16
+// consecutive rows, ds_write_b64) fall on 16 distinct bank pairs; B as the 16-deep image.
+constexpr int SA8 = 9;
+constexpr int CON_RING_A = T128 * SA8;          // 1152
+constexpr int CON_RING_SUB = CON_RING_A + (BK / 2) * SB;   // 2304 (every image 16-byte aligned)
+constexpr int CON_LDS_RING = 4 * CON_RING_SUB;  // 9216 doubles: two workgroups per CU still fit
+constexpr int CON_RING_NRD = 4;   // hipcc pairs the fragment reads: 2 A + 2 B ds_read2_b64
+constexpr int CON_RING_NWR = 4;   // 2 ds_write2_b64 (A) + 2 ds_write_b128 (B)
+// The instantiations that take the ring: VI's one-tile gradient contraction (no K u fold, whole
+// k range).  The K u fold reads the staged values at the top of the next step, the Stream-K
+// ranges start and end anywhere: both keep the two-stage loop.
+template <bool FROM_T, bool KU, int SKM, bool VIF>
+constexpr bool con_ring() {
+  return SGP_CON_RING && VIF && !KU && !FROM_T && SKM == 0;
+}
+
 // The part of a tile's k range one workgroup computes (k_contract_sk, the balanced launch): the
 // whole range (CON_FULL, also every tile of k_contract), its tail (CON_TAIL: the partial product
 // and partial K u are handed to the workgroup that holds the head, no epilogue) or its head
@@ -1181,6 +1384,7 @@ __device__ __forceinline__ void con_tile(
   const bool with_u = KU && (uvec != nullptr) && (ca.alpha_in == nullptr);   // fuse K u into the loop
   constexpr bool with_v = V2;   // second rank-1 term (Laplace), compiled in only where used
   constexpr bool NOCS = VIF && !KNOT;   // no column sums in the epilogue
+  constexpr bool RING = con_ring<FROM_T, KU, SKM, VIF>();   // `lds` then holds CON_LDS_RING
 
   d4 acc[4][4];
 #pragma unroll
@@ -1244,6 +1448,85 @@ __device__ __forceinline__ void con_tile(
         for (int q = 0; q < 4; ++q)
           acc[fm][fn][q] = ca.tin[(i0 + wr * 64 + fm * 16 + (lane >> 4) + 4 * q) * mp + j0 +
                                   wc * 64 + fn * 16 + (lane & 15)];
+  } else if constexpr (RING) {
+    // Ring of four 8-deep sub-stages: a sub-stage is complete in LDS one barrier before its
+    // first use.  During sub-step j a wave runs the 32 MFMAs of sub-stage j -- the first
+    // k-slice's fragments are in registers already -- reads the second slice of j, then the
+    // first slice of j + 1 (complete since the barrier that ended j - 1), so it leaves every
+    // barrier with MFMAs to issue; it loads sub-stage j + 3 into one staging set at the top
+    // and stores j + 2 from the other late in the sub-step (load-to-store distance 1.75
+    // sub-steps; 1.5 in the plain loop).  Per accumulator the MFMAs run in the plain loop's k
+    // order: the results are the same bits.  Four sub-steps per iteration, so every buffer and
+    // staging set is a compile-time choice; ke - kb is even (mp / BK is a multiple of 8).
+    // A loader: 16 consecutive lanes take 16 consecutive rows, 4 doubles at (tid >> 4 & 1) * 4
+    const int rrow = (tid & 15) + 16 * (tid >> 5), rh = ((tid >> 4) & 1) * 4;
+    const double2* rA = reinterpret_cast<const double2*>(K + (i0 + rrow) * mp + rh);
+    // B loader: 8 k x 128 cols, thread -> (k = tid >> 5, double2 columns (tid & 31) + 32 q)
+    const int rbk = tid >> 5, rbc = tid & 31;
+    const double2* rB = reinterpret_cast<const double2*>(M + (int64_t)rbk * mp + j0) + rbc;
+    const int64_t rbstep = (BK / 2) * mp / 2;
+    double2 pa0, pa1, pb0, pb1;   // staging set of the even sub-stages
+    double2 qa0, qa1, qb0, qb1;   // and of the odd ones
+    double a0[4], b0[4];          // first k-slice of the current sub-stage
+#define RING_LOAD(sub_, A0, A1, B0, B1)                                          \
+  {                                                                              \
+    const int64_t oa_ = (int64_t)(sub_) * (BK / 4), ob_ = (int64_t)(sub_) * rbstep; \
+    A0 = rA[oa_]; A1 = rA[oa_ + 1]; B0 = rB[ob_]; B1 = rB[ob_ + 32];             \
+  }
+#define RING_STORE(buf_, A0, A1, B0, B1)                                         \
+  {                                                                              \
+    double* As_ = lds + (buf_) * CON_RING_SUB;                                   \
+    double* pa_ = &As_[rrow * SA8 + rh];                                         \
+    double2* pb_ = reinterpret_cast<double2*>(&As_[CON_RING_A + rbk * SB]) + rbc; \
+    pa_[0] = A0.x; pa_[1] = A0.y; pa_[2] = A1.x; pa_[3] = A1.y;                  \
+    pb_[0] = B0; pb_[32] = B1;                                                   \
+  }
+#define RING_READ(buf_, sl_, AF, BF)                                             \
+  _Pragma("unroll") for (int f = 0; f < 4; ++f) {                                \
+    const double* As_ = lds + (buf_) * CON_RING_SUB;                             \
+    const int kx_ = (sl_) * 4 + (lane >> 4);                                     \
+    AF[f] = As_[(wr * 64 + f * 16 + (lane & 15)) * SA8 + kx_];                   \
+    BF[f] = As_[CON_RING_A + kx_ * SB + wc * 64 + f * 16 + (lane & 15)];         \
+  }
+#define RING_MFMA(AF, BF)                                                        \
+  _Pragma("unroll") for (int fm = 0; fm < 4; ++fm)                               \
+    _Pragma("unroll") for (int fn = 0; fn < 4; ++fn)                             \
+      acc[fm][fn] = __builtin_amdgcn_mfma_f64_16x16x4f64(AF[fm], BF[fn], acc[fm][fn], 0, 0, 0);
+    // sub-step j_ (j_ % 4 == R_): loads j_ + 3 into L (the last sub-stage again at the end:
+    // one basic block), stores j_ + 2 from S
+#define RING_SUB(j_, R_, L0, L1, L2, L3, S0, S1, S2, S3)                         \
+  {                                                                              \
+    RING_LOAD((j_) + 3 < sub_end ? (j_) + 3 : sub_end - 1, L0, L1, L2, L3);      \
+    double a1_[4], b1_[4], na_[4], nb_[4];                                       \
+    RING_READ(R_, 1, a1_, b1_);                                                  \
+    RING_MFMA(a0, b0);                                                           \
+    RING_READ(((R_) + 1) & 3, 0, na_, nb_);                                      \
+    RING_MFMA(a1_, b1_);                                                         \
+    RING_STORE(((R_) + 2) & 3, S0, S1, S2, S3);                                  \
+    ring_interleave<CON_RING_NRD, CON_RING_NWR>();                               \
+    __syncthreads();                                                             \
+    __builtin_amdgcn_sched_barrier(0);                                           \
+    _Pragma("unroll") for (int f = 0; f < 4; ++f) { a0[f] = na_[f]; b0[f] = nb_[f]; } \
+  }
+    const int sub_beg = 2 * kb, sub_end = 2 * ke;
+    RING_LOAD(sub_beg, pa0, pa1, pb0, pb1);
+    RING_LOAD(sub_beg + 1, qa0, qa1, qb0, qb1);
+    RING_STORE(0, pa0, pa1, pb0, pb1);
+    RING_STORE(1, qa0, qa1, qb0, qb1);
+    RING_LOAD(sub_beg + 2, pa0, pa1, pb0, pb1);
+    __syncthreads();
+    RING_READ(0, 0, a0, b0);
+    for (int j = sub_beg; j < sub_end; j += 4) {
+      RING_SUB(j, 0, qa0, qa1, qb0, qb1, pa0, pa1, pb0, pb1);
+      RING_SUB(j + 1, 1, pa0, pa1, pb0, pb1, qa0, qa1, qb0, qb1);
+      RING_SUB(j + 2, 2, qa0, qa1, qb0, qb1, pa0, pa1, pb0, pb1);
+      RING_SUB(j + 3, 3, pa0, pa1, pb0, pb1, qa0, qa1, qb0, qb1);
+    }
+#undef RING_SUB
+#undef RING_MFMA
+#undef RING_READ
+#undef RING_STORE
+#undef RING_LOAD
   } else {
   CON_GLOAD(kb);
   CON_SSTORE(0);
@@ -1707,7 +1990,8 @@ k_contract(KernParams kp, const double* __restrict__ K, const double* __restrict
            const double* __restrict__ X, int64_t ldx, int64_t n, int64_t n_pad,
            const double* __restrict__ U, int64_t ldu, int64_t m, int64_t mp, ConArgs ca,
            double* __restrict__ slab, int nrec, double* __restrict__ rowq) {
-  __shared__ __attribute__((aligned(16))) double lds[CON_LDS];
+  __shared__ __attribute__((aligned(16))) double
+      lds[con_ring<FROM_T, KU, 0, VIF>() ? CON_LDS_RING : CON_LDS];
   __shared__ double red[4][SGP_MAXD + 5];
   __shared__ double s_uk[2][BK];   // u slice of the staged k-step (fused alpha)
   const int64_t ntj = mp / T128;

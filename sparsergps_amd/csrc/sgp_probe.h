@@ -18,6 +18,8 @@
 //   SGP_CON_IL_PAT      LDS-store placement of the contraction's k-step (mfma_interleave PAT)
 //   SGP_SYRK_IL_PAT     the same for the SYRKs
 //   SGP_CON_IL_SPREAD   contraction: LDS fragment reads spread over the step instead of up front
+//   SGP_CON_RING        0: VI's gradient contraction keeps the two-stage k-loop (no ring)
+//   SGP_SYRK_RING       0: the work-balanced SYRK (k_syrk_bal) keeps the two-stage k-loop (no ring)
 //   SGP_CON_SHMEM       dynamic LDS pad of the gradient-contraction launches
 //   SGP_SYRK_BAL        0: no balanced S-only SYRK plan (syrk_plan_bal)
 //   SGP_SYRK_WB         0: VI's unweighted S without the work-balanced plan (sgp_syrk_plan.h)
@@ -56,7 +58,8 @@
      defined(SGP_GJ_STEPS) || defined(SGP_GJ_GMAX) || defined(SGP_CHAIN_US_STEP) ||         \
      defined(SGP_CHAIN_US_FIX) || defined(SGP_HOST_PROBE) || defined(SGP_BUILD_OCC_T2) ||      \
      defined(SGP_CON_EPI_PRIO) || defined(SGP_CON_PROBE_NO_EPI_MFMA) ||                       \
-     defined(SGP_CON_PROBE_NO_KDMA)) &&      \
+     defined(SGP_CON_PROBE_NO_KDMA) || defined(SGP_CON_RING) ||       \
+     defined(SGP_SYRK_RING)) &&      \
     !defined(SGP_PROBE_BUILD)
 #error "timing probes and experiment knobs are for variant builds only (SGP_PROBE_BUILD)"
 #endif
@@ -81,6 +84,12 @@
 #endif
 #ifndef SGP_CON_SHMEM
 #define SGP_CON_SHMEM 0
+#endif
+#ifndef SGP_CON_RING
+#define SGP_CON_RING 1
+#endif
+#ifndef SGP_SYRK_RING
+#define SGP_SYRK_RING 1
 #endif
 #ifndef SGP_SYRK_BAL
 #define SGP_SYRK_BAL 1

@@ -4,6 +4,8 @@
 // share a CU can be read off.  Synthetic operands; default n = 131072 rows, m = 1024, d = 8
 // (ARD); C2's shape is n = 100000, m = 256.
 //   build: hipcc -O3 --offload-arch=gfx950 -std=c++17 -o con_trace con_trace.hip
+//   -DCT_VIF: VI's instantiation (no K u fold: the ring k-loop; with -DSGP_CON_RING=0 the
+//   two-stage loop); -DSGP_CON_NO_EPILOGUE: the k-loops alone
 //   run:   ./con_trace out.csv [n m]
 #include <cstdio>
 #include <vector>
@@ -20,6 +22,11 @@ __device__ unsigned long long* g_trace;
                           (unsigned long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)); \
   } while (0)
 #include "../../sparsergps_amd/csrc/k_mfma.hip"
+#ifdef CT_VIF
+#define CT_KERNEL k_contract<8, EPI_GRAD, false, false, false, false, false, true>
+#else
+#define CT_KERNEL k_contract<8, EPI_GRAD>
+#endif
 
 // medians of the per-workgroup phases of the last launch (s_memtime ticks: shader clock)
 static void report(const char* tag, const unsigned long long* tr, int64_t nwg, int64_t n,
@@ -98,13 +105,16 @@ int main(int argc, char** argv) {
   for (int c = 0; c < d; ++c) { kp.l[c] = 3; kp.rl[c] = 1.0 / 3; kp.rl2[c] = 1.0 / 9; }
   ConArgs ca;
   ca.r = r; ca.invz = 4.0; ca.uvec = uv; ca.cdiag = cd; ca.count_a2 = 1; ca.alpha_out = alpha;
+#ifdef CT_VIF
+  ca.vi_fold = true;
+#endif
   int64_t nrec, nw;
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
   // one workgroup per CU: pad the launch with dynamic LDS so a second one cannot fit
   for (int it = 0; it < 3; ++it) {
     hipEventRecord(e0, 0);
-    hipLaunchKernelGGL((k_contract<8, EPI_GRAD>), dim3((unsigned)nwg), dim3(256), 80 * 1024, 0,
+    hipLaunchKernelGGL((CT_KERNEL), dim3((unsigned)nwg), dim3(256), 80 * 1024, 0,
                        kp, K, M, X, n_pad, n, n_pad, Uu, mp, m, mp, ca, slab, (int)(kp.L + 5),
                        (double*)nullptr);
     hipEventRecord(e1, 0);

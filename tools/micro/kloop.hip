@@ -8,6 +8,8 @@
 //   MODE 3  no barrier (fragment reads + MFMA only)
 //   MODE 4  MFMA only (fragments in registers)
 //   MODE 5  LDS-DMA staging (k_loop_dma)
+//   MODE 8  ring of four 8-deep sub-stages, fragments prefetched across the barrier
+//           (k_loop_ring; KLOOP_RING=1 runs it against MODE 0 and IL 1)
 // k_loop8: the same tile with 8 waves per workgroup (64 x 32 per wave).  MI355X r1: MODE 2
 // 74.4 vs 73.1 TF/s, but the full loop 68.1 vs 69.2 (the 4-wave loop stays)
 //   build: hipcc -O3 --offload-arch=gfx950 -std=c++17 -o kloop kloop.hip ; run: ./kloop
@@ -17,6 +19,8 @@
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 constexpr int BK = 16, SB = 144;
+// when set (KLOOP_RING's check): k_loop and k_loop_ring store every thread's accumulator sum
+__device__ double* d_chk = nullptr;
 
 // EPI > 0: a stand-in for the contraction's per-tile epilogue every 64 steps (one m = 1024 tile):
 // the waves wait for their accumulators, then sleep EPI x s_sleep(127) (~8k cycles each) without
@@ -120,6 +124,7 @@ __global__ void __launch_bounds__(256, 2) k_loop(const double* __restrict__ K, i
   for (int a = 0; a < 4; ++a)
     for (int b = 0; b < 4; ++b) s += acc[a][b][0] + acc[a][b][1] + acc[a][b][2] + acc[a][b][3];
   if (s == 1234.5) out[tid] = s;
+  if (d_chk) d_chk[(int64_t)blockIdx.x * 256 + tid] = s;
 }
 
 // Prefetch distance 2: global loads for step + 2 are issued at the top of step (two staging
@@ -217,7 +222,7 @@ void run_pf2(const double* K, int64_t mp, int nsteps, double* out, int nwg = 512
 // MFMA, then one LDS read, ... with the eight global loads and eight LDS stores spread over
 // the step -- the other instructions issue in the shadow of the MFMAs already in the pipe,
 // which matters when a wave has its SIMD to itself.  IL: 0 = no pattern (control).
-template <int IL>
+template <int IL, int EPI = 0>
 __global__ void __launch_bounds__(256, 2) k_loop_il(const double* __restrict__ K, int64_t mp,
                                                     int nsteps, double* out) {
   __shared__ __attribute__((aligned(16))) double Ka[2][BK * SB];
@@ -293,6 +298,7 @@ __global__ void __launch_bounds__(256, 2) k_loop_il(const double* __restrict__ K
       }
     }
     __syncthreads();
+    if (EPI > 0 && (step & 63) == 63) fake_epilogue(EPI, acc[0][0][0] + acc[3][3][3], out);
   }
   double s = 0.0;
   for (int a = 0; a < 4; ++a)
@@ -300,18 +306,152 @@ __global__ void __launch_bounds__(256, 2) k_loop_il(const double* __restrict__ K
   if (s == 1234.5) out[tid] = s;
 }
 
-template <int IL>
+template <int IL, int EPI = 0>
 void run_il(const double* K, int64_t mp, int nsteps, double* out, int nwg) {
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
-  hipLaunchKernelGGL(k_loop_il<IL>, dim3(nwg), dim3(256), 0, 0, K, mp, nsteps / 4, out);
+  hipLaunchKernelGGL((k_loop_il<IL, EPI>), dim3(nwg), dim3(256), 0, 0, K, mp, nsteps / 4, out);
   hipEventRecord(e0);
-  hipLaunchKernelGGL(k_loop_il<IL>, dim3(nwg), dim3(256), 0, 0, K, mp, nsteps, out);
+  hipLaunchKernelGGL((k_loop_il<IL, EPI>), dim3(nwg), dim3(256), 0, 0, K, mp, nsteps, out);
   hipEventRecord(e1);
   hipEventSynchronize(e1);
   float ms; hipEventElapsedTime(&ms, e0, e1);
   const double flops = 2.0 * 128 * 128 * 16 * (double)nsteps * nwg;
-  printf("IL %d wgs %d: %.3f ms  %.2f TF/s\n", IL, nwg, ms, flops / (ms * 1e-3) / 1e12);
+  if (EPI > 0)
+    printf("IL %d EPI %2d wgs %d: %.3f ms  %.2f TF/s\n", IL, EPI, nwg, ms,
+           flops / (ms * 1e-3) / 1e12);
+  else
+    printf("IL %d wgs %d: %.3f ms  %.2f TF/s\n", IL, nwg, ms, flops / (ms * 1e-3) / 1e12);
+}
+
+// MODE 8 (k_loop_ring): the LDS of the two 16-deep stages as a ring of four 8-deep sub-stages,
+// so that a sub-stage is complete one barrier before its first use.  During sub-step j a wave
+// runs the 32 MFMAs of sub-stage j (its first k-slice's fragments already in registers), reads
+// the second slice of j and then the first slice of j + 1 (complete since the barrier at the end
+// of j - 1): it leaves the barrier with 16 MFMAs issuable instead of waiting for that step's
+// first LDS reads.  It stores sub-stage j + 2 late in the sub-step from one of two staging
+// register sets and loads j + 3 into the other at the top (load-to-store distance 1.75
+// sub-steps; the plain loop's is 0.75 of a step = 1.5 sub-steps).  Per accumulator the MFMAs
+// run in the plain loop's k order.  Four sub-steps per loop iteration: every buffer and staging
+// set is a compile-time choice.  EPI > 0: a tile is 128 sub-stages, with the ring's drain and
+// prologue around every stand-in epilogue, as the contraction would have them.
+// PAT: the issue-order request of a sub-step (32 MFMAs, 4 global loads, 16 + 16 LDS reads,
+// 4 LDS stores) -- 0: the next sub-stage's reads behind MFMA 16 (their registers are the
+// first slice's), 1: behind MFMA 4, 2: no request.
+template <int PAT>
+__device__ __forceinline__ void ring_interleave() {
+#pragma unroll
+  for (int i = 0; i < 32; ++i) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                       // MFMA
+    if (i < 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);            // VMEM read
+    // hipcc pairs the fragment reads (ds_read2_b64): 4 instructions per slice
+    if (i < 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);            // DS read, slice 1
+    constexpr int r0 = PAT == 1 ? 4 : 16;
+    if (i >= r0 && i < r0 + 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // next slice 0
+    if (i >= 24 && i < 28) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);       // DS write
+  }
+}
+
+template <int EPI, int PAT>
+__global__ void __launch_bounds__(256, 2) k_loop_ring(const double* __restrict__ K, int64_t mp,
+                                                      int nsteps, double* out) {
+  constexpr int HK = 8;
+  __shared__ __attribute__((aligned(16))) double Ka[4][HK * SB];
+  __shared__ __attribute__((aligned(16))) double Kb[4][HK * SB];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int wr = wv >> 1, wc = wv & 1;
+  const int ta = blockIdx.x % 8, tb = (blockIdx.x / 8) % 8;
+  const int64_t rbeg = (int64_t)(blockIdx.x / 64) * nsteps * BK;
+  d4 acc[4][4];
+  for (int a = 0; a < 4; ++a)
+    for (int b = 0; b < 4; ++b) acc[a][b] = d4{0.0, 0.0, 0.0, 0.0};
+  const int lrow = tid >> 5, lc = tid & 31;   // 8 rows x 64 double2 per operand and sub-stage
+  const double2* gA = reinterpret_cast<const double2*>(K + (rbeg + lrow) * mp + ta * 128) + lc;
+  const double2* gB = reinterpret_cast<const double2*>(K + (rbeg + lrow) * mp + tb * 128) + lc;
+  const int64_t gsub = HK * mp / 2;
+  double2 pa0, pa1, pb0, pb1;   // staging set of the even sub-stages
+  double2 qa0, qa1, qb0, qb1;   // and of the odd ones
+  double a0[4], b0[4];          // first k-slice of the current sub-stage
+#define RING_LOAD(sub_, A0, A1, B0, B1)                                   \
+  {                                                                       \
+    const int64_t o_ = (int64_t)(sub_) * gsub;                            \
+    A0 = gA[o_]; A1 = gA[o_ + 32]; B0 = gB[o_]; B1 = gB[o_ + 32];         \
+  }
+#define RING_STORE(buf_, A0, A1, B0, B1)                                  \
+  {                                                                       \
+    double2* pa_ = reinterpret_cast<double2*>(&Ka[buf_][lrow * SB]) + lc; \
+    double2* pb_ = reinterpret_cast<double2*>(&Kb[buf_][lrow * SB]) + lc; \
+    pa_[0] = A0; pa_[32] = A1; pb_[0] = B0; pb_[32] = B1;                 \
+  }
+#define RING_READ(buf_, sl_, AF, BF)                                      \
+  _Pragma("unroll") for (int f = 0; f < 4; ++f) {                         \
+    AF[f] = Ka[buf_][((sl_) * 4 + (lane >> 4)) * SB + wr * 64 + f * 16 + (lane & 15)]; \
+    BF[f] = Kb[buf_][((sl_) * 4 + (lane >> 4)) * SB + wc * 64 + f * 16 + (lane & 15)]; \
+  }
+#define RING_MFMA(AF, BF)                                                 \
+  _Pragma("unroll") for (int fm = 0; fm < 4; ++fm)                        \
+    _Pragma("unroll") for (int fn = 0; fn < 4; ++fn)                      \
+      acc[fm][fn] = __builtin_amdgcn_mfma_f64_16x16x4f64(AF[fm], BF[fn], acc[fm][fn], 0, 0, 0);
+  // sub-step j_ (j_ % 4 == R_): loads j_ + 3 into L, stores j_ + 2 from S
+#define RING_SUB(j_, R_, L0, L1, L2, L3, S0, S1, S2, S3)                  \
+  {                                                                       \
+    const int nx_ = (j_) + 3 < sub_end ? (j_) + 3 : sub_end - 1;          \
+    RING_LOAD(nx_, L0, L1, L2, L3);                                       \
+    double a1_[4], b1_[4], na_[4], nb_[4];                                \
+    RING_READ(R_, 1, a1_, b1_);                                           \
+    RING_MFMA(a0, b0);                                                    \
+    RING_READ(((R_) + 1) & 3, 0, na_, nb_);                               \
+    RING_MFMA(a1_, b1_);                                                  \
+    RING_STORE(((R_) + 2) & 3, S0, S1, S2, S3);                           \
+    if (PAT != 2) ring_interleave<PAT>();                                 \
+    __syncthreads();                                                      \
+    __builtin_amdgcn_sched_barrier(0);                                    \
+    _Pragma("unroll") for (int f = 0; f < 4; ++f) { a0[f] = na_[f]; b0[f] = nb_[f]; } \
+  }
+  const int nsub = 2 * nsteps;                 // a multiple of 4
+  const int tile = EPI > 0 ? 128 : nsub;
+  for (int t0 = 0; t0 < nsub; t0 += tile) {
+    const int sub_end = t0 + tile < nsub ? t0 + tile : nsub;
+    RING_LOAD(t0, pa0, pa1, pb0, pb1);
+    RING_LOAD(t0 + 1, qa0, qa1, qb0, qb1);
+    RING_STORE(0, pa0, pa1, pb0, pb1);
+    RING_STORE(1, qa0, qa1, qb0, qb1);
+    RING_LOAD(t0 + 2, pa0, pa1, pb0, pb1);
+    __syncthreads();
+    RING_READ(0, 0, a0, b0);
+    for (int j = t0; j < sub_end; j += 4) {
+      RING_SUB(j, 0, qa0, qa1, qb0, qb1, pa0, pa1, pb0, pb1);
+      RING_SUB(j + 1, 1, pa0, pa1, pb0, pb1, qa0, qa1, qb0, qb1);
+      RING_SUB(j + 2, 2, qa0, qa1, qb0, qb1, pa0, pa1, pb0, pb1);
+      RING_SUB(j + 3, 3, pa0, pa1, pb0, pb1, qa0, qa1, qb0, qb1);
+    }
+    if (EPI > 0) fake_epilogue(EPI, acc[0][0][0] + acc[3][3][3], out);
+  }
+#undef RING_SUB
+#undef RING_MFMA
+#undef RING_READ
+#undef RING_STORE
+#undef RING_LOAD
+  double s = 0.0;
+  for (int a = 0; a < 4; ++a)
+    for (int b = 0; b < 4; ++b) s += acc[a][b][0] + acc[a][b][1] + acc[a][b][2] + acc[a][b][3];
+  if (s == 1234.5) out[tid] = s;
+  if (d_chk) d_chk[(int64_t)blockIdx.x * 256 + tid] = s;
+}
+
+template <int EPI, int PAT>
+void run_ring(const double* K, int64_t mp, int nsteps, double* out, int nwg) {
+  hipEvent_t e0, e1;
+  hipEventCreate(&e0); hipEventCreate(&e1);
+  hipLaunchKernelGGL((k_loop_ring<EPI, PAT>), dim3(nwg), dim3(256), 0, 0, K, mp, nsteps / 4, out);
+  hipEventRecord(e0);
+  hipLaunchKernelGGL((k_loop_ring<EPI, PAT>), dim3(nwg), dim3(256), 0, 0, K, mp, nsteps, out);
+  hipEventRecord(e1);
+  hipEventSynchronize(e1);
+  float ms; hipEventElapsedTime(&ms, e0, e1);
+  const double flops = 2.0 * 128 * 128 * 16 * (double)nsteps * nwg;
+  printf("MODE 8 (ring) PAT %d EPI %2d wgs %d: %.3f ms  %.2f TF/s\n", PAT, EPI, nwg, ms,
+         flops / (ms * 1e-3) / 1e12);
 }
 
 // BK = 32 per step, double-buffered, one workgroup per CU (launch_bounds(256, 1): up to 512
@@ -586,6 +726,67 @@ int main() {
     free(h);
   }
   const int nsteps = 4000;
+  if (getenv("KLOOP_RING")) {
+    // the ring (MODE 8) against the plain loop (MODE 0) and the product's interleaved loop
+    // (IL 1), alternating in one process after >= 2 s of warm launches: paired (512
+    // workgroups) and alone (256), without and with a stand-in epilogue per 64 steps
+    {
+      hipEvent_t w0, w1;
+      hipEventCreate(&w0); hipEventCreate(&w1);
+      float ms = 0.f;
+      hipEventRecord(w0);
+      while (ms < 2500.f) {
+        for (int i = 0; i < 8; ++i)
+          hipLaunchKernelGGL((k_loop<0, 0>), dim3(512), dim3(256), 0, 0, K, mp, nsteps, out);
+        hipEventRecord(w1);
+        hipEventSynchronize(w1);
+        hipEventElapsedTime(&ms, w0, w1);
+      }
+      printf("warm: %.0f ms of MODE 0\n", ms);
+    }
+    {
+      // the ring sums in the plain loop's order: every thread's accumulator sum is the same bits
+      const size_t nc = 512 * 256;
+      double *c0, *c1, *h0 = (double*)malloc(nc * 8), *h1 = (double*)malloc(nc * 8);
+      hipMalloc(&c0, nc * 8); hipMalloc(&c1, nc * 8);
+      (void)hipMemcpyToSymbol(HIP_SYMBOL(d_chk), &c0, sizeof(c0));
+      hipLaunchKernelGGL((k_loop<0, 0>), dim3(512), dim3(256), 0, 0, K, mp, 200, out);
+      (void)hipMemcpy(h0, c0, nc * 8, hipMemcpyDeviceToHost);
+      (void)hipMemcpyToSymbol(HIP_SYMBOL(d_chk), &c1, sizeof(c1));
+      auto cmp = [&](const char* what) {
+        (void)hipMemcpy(h1, c1, nc * 8, hipMemcpyDeviceToHost);
+        size_t bad = 0;
+        for (size_t i = 0; i < nc; ++i) bad += h0[i] != h1[i];
+        printf("check %s against MODE 0: %zu of %zu sums differ (first %.17g)\n", what, bad, nc,
+               h1[0]);
+      };
+      hipLaunchKernelGGL((k_loop_ring<0, 0>), dim3(512), dim3(256), 0, 0, K, mp, 200, out);
+      cmp("ring PAT 0");
+      hipLaunchKernelGGL((k_loop_ring<0, 1>), dim3(512), dim3(256), 0, 0, K, mp, 200, out);
+      cmp("ring PAT 1");
+      hipLaunchKernelGGL((k_loop_ring<0, 2>), dim3(512), dim3(256), 0, 0, K, mp, 200, out);
+      cmp("ring PAT 2");
+      hipLaunchKernelGGL((k_loop_ring<6, 0>), dim3(512), dim3(256), 0, 0, K, mp, 200, out);
+      cmp("ring PAT 0 in tiles");
+      double* none = nullptr;
+      (void)hipMemcpyToSymbol(HIP_SYMBOL(d_chk), &none, sizeof(none));
+      hipFree(c0); hipFree(c1); free(h0); free(h1);
+    }
+    for (int rep = 0; rep < 5; ++rep) {
+      for (int nwg = 512; nwg >= 256; nwg -= 256) {
+        run<0>(K, mp, nsteps, out, nwg);
+        run_il<1>(K, mp, nsteps, out, nwg);
+        run_ring<0, 0>(K, mp, nsteps, out, nwg);
+        run_ring<0, 1>(K, mp, nsteps, out, nwg);
+        run_ring<0, 2>(K, mp, nsteps, out, nwg);
+        run<0, 6>(K, mp, nsteps, out, nwg);
+        run_il<1, 6>(K, mp, nsteps, out, nwg);
+        run_ring<6, 0>(K, mp, nsteps, out, nwg);
+        run_ring<6, 1>(K, mp, nsteps, out, nwg);
+      }
+    }
+    return 0;
+  }
   if (getenv("KLOOP_ALONE")) {   // one workgroup per CU (one wave per SIMD) vs two
     for (int rep = 0; rep < 2; ++rep) {
       run_il<0>(K, mp, nsteps, out, 512);
