@@ -123,7 +123,8 @@ int sgp_ctx_destroy(sgp_ctx* ctx);
  * in the global row order) / sgp_lap_objective_values, sgp_posterior_u, sgp_ctx_enable_knot_grad,
  * sgp_knot_gradient (bounds NULL = the knot bounds of ALL rows), sgp_ctx_row_bounds (all rows),
  * sgp_ctx_set_data, sgp_ctx_rows (all rows), the three candidate scorers (each VI candidate as an
- * objective-only evaluation at [U; cand_t], m + 1 <= m_max), the timing calls (shard 0's
+ * objective-only evaluation at [U; cand_t], m + 1 <= m_max), sgp_ego_scan (shard by shard; the
+ * winner over all rows, vectors in the global row order), the timing calls (shard 0's
  * record) and sgp_ctx_destroy.  The phase-level entry points (sgp_vi_phase1 ... sgp_lap_step),
  * sgp_ctx_set_stream, sgp_ctx_set_packed_reduction, sgp_eval_full, sgp_eval_full_laplace and
  * sgp_full_laplace_state return SGP_EINVAL.
@@ -366,6 +367,42 @@ int sgp_fitc_candidates(sgp_ctx* ctx, int kernel, const double* theta, const dou
 int sgp_lap_candidates(sgp_ctx* ctx, int kernel, const double* theta, const double* U, int64_t m,
                        int64_t ldu, double delta, double expo, double tol, int maxit,
                        const double* cand, int64_t T, int64_t ldc, double* obj_out);
+
+/* The EGO knot proposal's scan (knot_prop_ego_norm_vi R/vi_functions.R:1927-1950, 2074-2097;
+ * knot_prop_ego_norm / knot_prop_ego R/knot_proposal_functions.R:355-379, 457-478, 832-855,
+ * 964-985): after every refit of the meta-model GP of the objective -- T points xm (T x d,
+ * column-major, ld ldxm) with objective values vals -- the reference predicts the objective at
+ * every data row outside the knots and takes the row of largest expected improvement:
+ *   K12 = make_cov_matC(xy_setminus_xu, xm)  (cross mode: no nugget, even on a coincident pair)
+ *   K22 = make_cov_matC(xm) = k(xm, xm) + (tau^2 + delta_meta) I   (the reference passes delta/1000)
+ *   pred_i = vals[0] + K12[i,] K22^-1 (vals - vals[0])
+ *   var_i  = sigma^2 + tau^2 - K12[i,] K22^-1 K12[i,]^T
+ *   EI_i   = sqrt(var_i) (z pnorm(z) + dnorm(z)), z = (pred_i - max vals) / sqrt(var_i), when
+ *            var_i > tau^2 (strictly; false for NaN), else 0;  pnorm(z) = erfc(-z / sqrt 2) / 2
+ *   best_row = which.max(EI) over the rows not in excl: ties to the lowest row, a NaN never wins,
+ *            all zero -> the first such row
+ * as one pass over the context's resident rows (R: one dense solve per row in a loop over n).
+ * kernel: SGP_KERNEL_EXP (the reference's default ego_cov_fun, L1 distance,
+ * src/covariance_functionsC.cpp:45-52) or SGP_KERNEL_SQEXP; SGP_KERNEL_ARD is refused (the
+ * reference's make_cov_matC returns a 0 x 0 matrix for it).  theta_meta = [sigma, l, tau] with
+ * sigma > 0, l > 0, tau >= 0 (the reference's default ego_cov_par$tau is 0); delta_meta >= 0.
+ * excl (E x d column-major, ld ldexcl, or NULL): a data row is excluded when all d of its
+ * coordinates equal (==) those of some row of excl -- the reference's xy_setminus_xu
+ * (vi_functions.R:1679-1687) with excl = the knots.  (The reference also drops data rows that
+ * duplicate earlier data rows; that cannot change the winner's coordinates.)
+ * best_row: 0-based row of the context's X; best_ei: its EI.  ei_out / mean_out / var_out: n host
+ * values each or NULL -- pred and var for every row, EI with NaN on the excluded rows.
+ * 1 <= T <= SGP_EGO_TMAX.  SGP_EINVAL before any device call for NULL arguments, T or a leading
+ * dimension out of range, non-finite vals / theta_meta / xm, sigma <= 0, l <= 0, tau < 0 or
+ * delta_meta < 0; SGP_EINVAL ("no data row outside the knots") when every row is excluded;
+ * SGP_ENOTPD naming "meta-model K22" when K22 is not positive definite.  A completed evaluation
+ * is left as it was (sgp_posterior_u still answers for it).  Multi-device contexts: rows and
+ * vectors in the global row order. */
+#define SGP_EGO_TMAX 128
+int sgp_ego_scan(sgp_ctx* ctx, int kernel, const double* theta_meta, double delta_meta,
+                 const double* xm, int64_t T, int64_t ldxm, const double* vals,
+                 const double* excl, int64_t E, int64_t ldexcl, int64_t* best_row,
+                 double* best_ei, double* ei_out, double* mean_out, double* var_out);
 
 /* Per-phase timing (HIP events on the launch stream).  Enabling clears the record; every
  * evaluation after it appends its phases, and sgp_ctx_timings returns the per-phase totals

@@ -42,6 +42,13 @@ int sgp_diag_store_bw(int device, int64_t bytes, int reps, int pattern, double* 
 int sgp_diag_syrk_plan(int64_t n, int64_t m, int* plan, int* workgroups, double* t_balanced,
                        double* t_packed);
 
+/* Host only (no device is touched): the argument checks sgp_ego_scan (sgp.h) runs before its
+ * first device call, for rows of dimension d -- the very function it calls, so a machine without
+ * a GPU can test every SGP_EINVAL case.  SGP_OK or SGP_EINVAL with sgp_last_error(). */
+int sgp_diag_ego_args(int d, int kernel, const double* theta_meta, double delta_meta,
+                      const double* xm, int64_t T, int64_t ldxm, const double* vals,
+                      const double* excl, int64_t E, int64_t ldexcl);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ from .full import (dlogp_dcov_par_full, dlogq_dcov_par_full, full_eval, full_lap
 from .predict import predict_gp, predict_laplace, predict_vi
 from .laplace import (dlogq_dcov_par, laplace_eval, newtrap_sparseGP, obj_fun_bern,
                       obj_fun_pois)
+from .proposals import knot_prop_ego, knot_prop_ego_norm, knot_prop_ego_norm_vi
 from .vi import (SparseGPContext, delbo_dcov_par, dlogp_dcov_par, elbo_fun, fitc_eval, param_names,
                  vi_eval)
 
@@ -30,4 +31,5 @@ __all__ = [
     "predict_gp_full",
     "full_laplace_eval", "newtrapGP", "obj_fun_pois_full", "obj_fun_bern_full",
     "dlogq_dcov_par_full", "laplace_grad_ascent_full", "predict_laplace_full",
+    "knot_prop_ego_norm_vi", "knot_prop_ego_norm", "knot_prop_ego",
 ]

@@ -77,6 +77,8 @@ PROTOTYPES = {
     "sgp_diag_store_bw": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, c_double_p]),
     "sgp_diag_syrk_plan": (C.c_int, [C.c_int64, C.c_int64, c_int_p, c_int_p, c_double_p,
                                      c_double_p]),
+    "sgp_diag_ego_args": (C.c_int, [C.c_int, C.c_int, c_double_p, C.c_double, c_double_p, C.c_int64,
+                                    C.c_int64, c_double_p, c_double_p, C.c_int64, C.c_int64]),
     "sgp_lap_get_f": (C.c_int, [C.c_void_p, c_double_p]),
     "sgp_lap_get_grad_psi": (C.c_int, [C.c_void_p, c_double_p]),
     "sgp_lap_objective_values": (C.c_int, [C.c_void_p, c_double_p, C.c_int, c_int_p]),
@@ -115,6 +117,10 @@ PROTOTYPES = {
     "sgp_lap_candidates": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p, C.c_int64,
                                      C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int,
                                      c_double_p, C.c_int64, C.c_int64, c_double_p]),
+    "sgp_ego_scan": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_double, c_double_p, C.c_int64,
+                               C.c_int64, c_double_p, c_double_p, C.c_int64, C.c_int64,
+                               C.POINTER(C.c_int64), c_double_p, c_double_p, c_double_p,
+                               c_double_p]),
     "sgp_ctx_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "sgp_ctx_timing_filter": (C.c_int, [C.c_void_p, C.c_char_p]),
     "sgp_ctx_timing_evals": (C.c_int64, [C.c_void_p]),

@@ -319,6 +319,16 @@ struct sgp_ctx {
   // full-GP Laplace (sgp_eval_full_laplace): FL_N x n_pad row vectors, allocated on first use
   double* fl = nullptr;
   bool fl_valid = false;                  // FL_W0 / FL_D10 hold a full-Laplace NR's returned state
+  // EGO scan (sgp_ego_scan): the meta-model's work space (EGO_* offsets), its chain's sync and
+  // status words, the three optional per-row vectors (3 x n_pad) and the sorted exclusion list;
+  // allocated on first use
+  double* ego = nullptr;
+  unsigned* ego_sync = nullptr;
+  int* ego_status = nullptr;
+  double* ego_rows = nullptr;
+  double* ego_ex = nullptr;
+  int64_t ego_ex_cap = 0;
+  int ego_blocks = 0;                     // workgroups of the scan: 8 per CU
   // timing
   bool timing = false;
   std::string timing_only;                // record only the scopes of this name ("" = all)
@@ -520,7 +530,8 @@ void ctx_free(sgp_ctx* c) {
                   c->y,      c->mu,     c->lv,     c->lm,    c->lslab, c->lred[0], c->lred[1],
                   c->Cprev,  c->lapAZ,  c->lapAB,  c->laprv,  c->fl,
                   c->knot_slab, c->knot_part, c->knot_kmm, c->tslab, c->tq, c->tp,
-                  c->rr_dev, c->Sfull, c->gjs, c->mmpart, c->rsync};
+                  c->rr_dev, c->Sfull, c->gjs, c->mmpart, c->rsync,
+                  c->ego,    c->ego_sync, c->ego_status, c->ego_rows, c->ego_ex};
   for (void* p : ptrs)
     if (p) hipFree(p);
   if (c->khash) hipFree(c->khash);
@@ -2926,6 +2937,254 @@ int sgp_posterior_u(sgp_ctx* c, const double* muu, double* u_mean, double* u_var
   for (int64_t j = 0; j < m; ++j) u_mean[j] = muu[j] + hv[(size_t)j];
   for (int64_t j = 0; j < m; ++j)
     for (int64_t i = 0; i < m; ++i) u_var[i + j * m] = hm[(size_t)(i * mp + j)];
+  return SGP_OK;
+}
+
+// ------------------------------------------------------------------------- EGO scan
+// The expected-improvement scan of the EGO knot proposals (include/sgp.h; k_ego.hip).
+namespace {
+// c->ego (doubles): meta points (128 x SGP_MAXD, column-major) | K22 | its inverse | chain scratch
+// R | pivot inverses P (128 x 64) | logd | v - v1 | alpha | out (8) | per-workgroup records
+constexpr int64_t EGO_TT = (int64_t)SGP_EGO_TMAX * SGP_EGO_TMAX;
+constexpr int64_t EGO_XM = 0, EGO_K22 = EGO_XM + (int64_t)SGP_EGO_TMAX * SGP_MAXD,
+                  EGO_INV = EGO_K22 + EGO_TT, EGO_R = EGO_INV + EGO_TT, EGO_P = EGO_R + EGO_TT,
+                  EGO_LOGD = EGO_P + (int64_t)SGP_EGO_TMAX * 64, EGO_VEC = EGO_LOGD + 8,
+                  EGO_ALPHA = EGO_VEC + SGP_EGO_TMAX, EGO_OUT = EGO_ALPHA + SGP_EGO_TMAX,
+                  EGO_REC = EGO_OUT + 8;
+constexpr int EGO_MAX_BLOCKS = 4096;
+constexpr int64_t EGO_DOUBLES = EGO_REC + 2 * EGO_MAX_BLOCKS;
+static_assert(SGP_EGO_TMAX == SGP_TILE, "the meta-model's K22 is one tile of dense_spd_inverse");
+
+int ego_check_args(int d, int kernel, const double* theta, double delta, const double* xm,
+                   int64_t T, int64_t ldxm, const double* vals, const double* excl, int64_t E,
+                   int64_t ldexcl) {
+  if (kernel == SGP_KERNEL_ARD) {
+    set_err("sgp_ego_scan supports 'exp' and 'sqexp' (the reference's make_cov_matC returns a "
+            "0 x 0 matrix for 'ard')");
+    return SGP_EINVAL;
+  }
+  if (kernel != SGP_KERNEL_SQEXP && kernel != SGP_KERNEL_EXP) {
+    set_err("invalid covariance function (kernel=%d)", kernel);
+    return SGP_EINVAL;
+  }
+  if (d < 1 || d > SGP_MAXD) {
+    set_err("input dimension d=%d outside [1, %d]", d, SGP_MAXD);
+    return SGP_EINVAL;
+  }
+  if (!theta || !xm || !vals) {
+    set_err("sgp_ego_scan: theta_meta, xm and vals must not be NULL");
+    return SGP_EINVAL;
+  }
+  if (T < 1 || T > SGP_EGO_TMAX) {
+    set_err("sgp_ego_scan: T=%lld outside [1, %d]", (long long)T, SGP_EGO_TMAX);
+    return SGP_EINVAL;
+  }
+  if (ldxm < T) {
+    set_err("sgp_ego_scan: ldxm=%lld < T=%lld", (long long)ldxm, (long long)T);
+    return SGP_EINVAL;
+  }
+  if (excl && (E < 0 || ldexcl < E)) {
+    set_err("sgp_ego_scan: invalid exclusion list (E=%lld, ldexcl=%lld)", (long long)E,
+            (long long)ldexcl);
+    return SGP_EINVAL;
+  }
+  for (int p = 0; p < 3; ++p)
+    if (!std::isfinite(theta[p])) {
+      set_err("sgp_ego_scan: theta_meta[%d] is not finite", p);
+      return SGP_EINVAL;
+    }
+  if (!(theta[0] > 0.0) || !(theta[1] > 0.0) || !(theta[2] >= 0.0)) {
+    set_err("sgp_ego_scan: needs sigma > 0, l > 0 and tau >= 0 (sigma=%g, l=%g, tau=%g)",
+            theta[0], theta[1], theta[2]);
+    return SGP_EINVAL;
+  }
+  if (!(delta >= 0.0) || !std::isfinite(delta)) {
+    set_err("sgp_ego_scan: delta_meta=%g is not a finite value >= 0", delta);
+    return SGP_EINVAL;
+  }
+  for (int64_t j = 0; j < T; ++j)
+    if (!std::isfinite(vals[j])) {
+      set_err("sgp_ego_scan: vals[%lld] is not finite", (long long)j);
+      return SGP_EINVAL;
+    }
+  for (int q = 0; q < d; ++q)
+    for (int64_t j = 0; j < T; ++j)
+      if (!std::isfinite(xm[j + q * ldxm])) {
+        set_err("sgp_ego_scan: xm[%lld, %d] is not finite", (long long)j, q);
+        return SGP_EINVAL;
+      }
+  return SGP_OK;
+}
+
+int ego_ensure(sgp_ctx* c, int64_t E) {
+  if (!c->ego) {
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    c->ego_blocks = std::min(EGO_MAX_BLOCKS, std::max(1, 8 * cus));
+    int st = dalloc(&c->ego_sync, SGP_GJ_SYNC_WORDS);
+    st = st ? st : dalloc(&c->ego_status, 4);
+    st = st ? st : dalloc(&c->ego_rows, 3 * c->n_pad);
+    st = st ? st : dalloc(&c->ego, EGO_DOUBLES);   // last: marks the set as complete
+    if (st) {
+      if (c->ego_sync) (void)hipFree(c->ego_sync);
+      if (c->ego_status) (void)hipFree(c->ego_status);
+      if (c->ego_rows) (void)hipFree(c->ego_rows);
+      c->ego_sync = nullptr;
+      c->ego_status = nullptr;
+      c->ego_rows = nullptr;
+      c->ego = nullptr;
+      return st;
+    }
+  }
+  const int64_t need = E * c->d;
+  if (need > c->ego_ex_cap) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->ego_ex) (void)hipFree(c->ego_ex);
+    c->ego_ex = nullptr;
+    c->ego_ex_cap = 0;
+    const int st = dalloc(&c->ego_ex, need);
+    if (st) return st;
+    c->ego_ex_cap = need;
+  }
+  return SGP_OK;
+}
+}  // namespace
+
+extern "C++" {   // sgp_multi.h hook
+// sgp_ego_scan on a one-device context (or one shard); *best_row = -1 when every row is excluded
+int sgp_internal_ego_scan(sgp_ctx* c, int kernel, const double* theta, double delta,
+                          const double* xm, int64_t T, int64_t ldxm, const double* vals,
+                          const double* excl, int64_t E, int64_t ldexcl, int64_t* best_row,
+                          double* best_ei, double* ei_out, double* mean_out, double* var_out) {
+  KernParams kp;
+  int st = make_params(kernel, c->d, theta, delta, &kp);
+  if (st) return st;
+  const int d = c->d;
+  constexpr int64_t TM = SGP_EGO_TMAX;
+  // exclusion list: the rows that can match something (no NaN), sorted by coordinate 0
+  std::vector<double> hex;
+  int64_t Ex = 0;
+  if (excl && E > 0) {
+    std::vector<int64_t> idx;
+    for (int64_t k = 0; k < E; ++k) {
+      bool ok = true;
+      for (int q = 0; q < d && ok; ++q) ok = !std::isnan(excl[k + q * ldexcl]);
+      if (ok) idx.push_back(k);
+    }
+    std::stable_sort(idx.begin(), idx.end(),
+                     [&](int64_t a, int64_t b) { return excl[a] < excl[b]; });
+    Ex = (int64_t)idx.size();
+    hex.resize((size_t)(Ex * d));
+    for (int q = 0; q < d; ++q)
+      for (int64_t k = 0; k < Ex; ++k) hex[(size_t)(k + q * Ex)] = excl[idx[(size_t)k] + q * ldexcl];
+  }
+  HIPCHK(hipSetDevice(c->device));
+  st = ego_ensure(c, Ex);
+  if (st) return st;
+  hipStream_t s = c->stream;
+  double vmax = vals[0];
+  std::vector<double> hxm((size_t)(TM * d), 0.0), hv((size_t)TM, 0.0);
+  for (int q = 0; q < d; ++q)
+    for (int64_t j = 0; j < T; ++j) hxm[(size_t)(q * TM + j)] = xm[j + q * ldxm];
+  for (int64_t j = 0; j < T; ++j) {
+    hv[(size_t)j] = vals[j] - vals[0];
+    vmax = vals[j] > vmax ? vals[j] : vmax;
+  }
+  double* w = c->ego;
+  timers_reset(c);
+  {
+    Scope sc(c, "ego_meta");   // uploads, K22, its inverse, alpha
+    // (the host buffers outlive the copies: every path below synchronises the stream or fails)
+    HIPCHK(hipMemcpyAsync(w + EGO_XM, hxm.data(), sizeof(double) * hxm.size(),
+                          hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(w + EGO_VEC, hv.data(), sizeof(double) * TM, hipMemcpyHostToDevice, s));
+    if (Ex > 0)
+      HIPCHK(hipMemcpyAsync(c->ego_ex, hex.data(), sizeof(double) * hex.size(),
+                            hipMemcpyHostToDevice, s));
+    // the chain's sync words must be zero when it starts (a failed chain may leave them set)
+    HIPCHK(hipMemsetAsync(c->ego_status, 0, sizeof(int) * 4, s));
+    HIPCHK(hipMemsetAsync(c->ego_sync, 0, sizeof(unsigned) * SGP_GJ_SYNC_WORDS, s));
+    // K22 = k(xm, xm) + (tau^2 + delta_meta) I, padded to the tile with a unit diagonal
+    HIPCHK(launch_build_kmm(kp, w + EGO_XM, TM, T, TM, 0.0, w + EGO_K22, s, w + EGO_INV));
+    HIPCHK(dense_spd_inverse(w + EGO_INV, TM, w + EGO_R, w + EGO_P, w + EGO_LOGD, c->ego_status,
+                             c->ego_sync, s));
+    HIPCHK(dense_gemv(w + EGO_INV, TM, w + EGO_VEC, 1.0, w + EGO_ALPHA, s));
+  }
+  EgoScan a;
+  a.X = c->X;
+  a.ldx = c->n_pad;
+  a.n = c->n;
+  a.d = d;
+  a.T = (int)T;
+  a.kexp = kernel == SGP_KERNEL_EXP ? 1 : 0;
+  a.coef = kp.coef;
+  a.sig2 = kp.sig2;
+  a.c0 = kp.sig2 + kp.tau2;
+  a.tau2 = kp.tau2;
+  a.v1 = vals[0];
+  a.vmax = vmax;
+  a.xm = w + EGO_XM;
+  a.Ainv = w + EGO_INV;
+  a.alpha = w + EGO_ALPHA;
+  a.ex = c->ego_ex;
+  a.E = Ex;
+  a.ei_out = ei_out ? c->ego_rows : nullptr;
+  a.mean_out = mean_out ? c->ego_rows + c->n_pad : nullptr;
+  a.var_out = var_out ? c->ego_rows + 2 * c->n_pad : nullptr;
+  a.rec = w + EGO_REC;
+  {
+    Scope sc(c, "ego_scan");   // the pass over X and its one-block final reduction
+    HIPCHK(launch_ego_scan(a, c->ego_blocks, c->ego_status, w + EGO_OUT, s));
+  }
+  double ho[3] = {0.0, -1.0, 0.0};
+  HIPCHK(hipMemcpyAsync(ho, w + EGO_OUT, sizeof(ho), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (ho[2] < 0.0) {
+    set_err("internal error: a Gauss-Jordan chain's wait watchdog expired");
+    return SGP_EHIP;
+  }
+  if (ho[2] != 0.0) {
+    set_err("meta-model K22 is not positive definite (leading minor of order %d)", (int)ho[2]);
+    return SGP_ENOTPD;
+  }
+  const size_t nb = sizeof(double) * (size_t)c->n;
+  if (ei_out) HIPCHK(hipMemcpyAsync(ei_out, a.ei_out, nb, hipMemcpyDeviceToHost, s));
+  if (mean_out) HIPCHK(hipMemcpyAsync(mean_out, a.mean_out, nb, hipMemcpyDeviceToHost, s));
+  if (var_out) HIPCHK(hipMemcpyAsync(var_out, a.var_out, nb, hipMemcpyDeviceToHost, s));
+  if (ei_out || mean_out || var_out) HIPCHK(hipStreamSynchronize(s));
+  *best_row = (int64_t)ho[1];
+  *best_ei = ho[0];
+  return SGP_OK;
+}
+}  // extern "C++"
+
+int sgp_diag_ego_args(int d, int kernel, const double* theta_meta, double delta_meta,
+                      const double* xm, int64_t T, int64_t ldxm, const double* vals,
+                      const double* excl, int64_t E, int64_t ldexcl) {
+  return ego_check_args(d, kernel, theta_meta, delta_meta, xm, T, ldxm, vals, excl, E, ldexcl);
+}
+
+int sgp_ego_scan(sgp_ctx* c, int kernel, const double* theta_meta, double delta_meta,
+                 const double* xm, int64_t T, int64_t ldxm, const double* vals,
+                 const double* excl, int64_t E, int64_t ldexcl, int64_t* best_row,
+                 double* best_ei, double* ei_out, double* mean_out, double* var_out) {
+  if (!c || !best_row || !best_ei) {
+    set_err("sgp_ego_scan: ctx, best_row and best_ei must not be NULL");
+    return SGP_EINVAL;
+  }
+  int st = ego_check_args(c->d, kernel, theta_meta, delta_meta, xm, T, ldxm, vals, excl, E, ldexcl);
+  if (st) return st;
+  if (c->multi)
+    st = multi_ego_scan(c->multi, kernel, theta_meta, delta_meta, xm, T, ldxm, vals, excl, E,
+                        ldexcl, best_row, best_ei, ei_out, mean_out, var_out);
+  else
+    st = sgp_internal_ego_scan(c, kernel, theta_meta, delta_meta, xm, T, ldxm, vals, excl, E,
+                               ldexcl, best_row, best_ei, ei_out, mean_out, var_out);
+  if (st) return st;
+  if (*best_row < 0) {
+    set_err("sgp_ego_scan: no data row outside the knots (every row is excluded)");
+    return SGP_EINVAL;
+  }
   return SGP_OK;
 }
 

@@ -595,6 +595,36 @@ int multi_lap_get_grad_psi(MultiCtx* mc, double* out) {
   return SGP_OK;
 }
 
+// ------------------------------------------------------------------------------ EGO scan
+// Shard by shard from the caller's thread (each repeats the small meta-model inverse); the
+// winner is the largest EI, ties to the lowest global row: shards are visited in row order and
+// a later shard must be strictly better.
+int multi_ego_scan(MultiCtx* mc, int kernel, const double* theta, double delta, const double* xm,
+                   int64_t T, int64_t ldxm, const double* vals, const double* excl, int64_t E,
+                   int64_t ldexcl, int64_t* best_row, double* best_ei, double* ei_out,
+                   double* mean_out, double* var_out) {
+  int64_t brow = -1;
+  double bei = 0.0;
+  for (Shard& s : mc->shards) {
+    int64_t row = -1;
+    double ei = 0.0;
+    const int st = sgp_internal_ego_scan(s.ctx, kernel, theta, delta, xm, T, ldxm, vals, excl, E,
+                                         ldexcl, &row, &ei, ei_out ? ei_out + s.row0 : nullptr,
+                                         mean_out ? mean_out + s.row0 : nullptr,
+                                         var_out ? var_out + s.row0 : nullptr);
+    if (st) return st;
+    if (row < 0) continue;
+    // a NaN EI (a shard whose every EI is NaN) never beats a number
+    if (brow < 0 || ei > bei || (bei != bei && ei == ei)) {
+      brow = s.row0 + row;
+      bei = ei;
+    }
+  }
+  *best_row = brow;
+  *best_ei = bei;
+  return SGP_OK;
+}
+
 // ------------------------------------------------------------------------------ knots
 int multi_enable_knot_grad(MultiCtx* mc, int enable) {
   for (Shard& s : mc->shards) {

@@ -8,6 +8,9 @@
 #define SGP_TILE 128         // n x m tile edge of the MFMA kernels (rows and knots padded to it)
 #define SGP_DB 64            // block edge of the m x m dense routines
 #define SGP_GJ_SYNC_WORDS (128 + 2 * 64 * 64)   // k_dense.hip: ticket, exits, flags (nb <= 64)
+#ifndef SGP_EGO_TMAX
+#define SGP_EGO_TMAX 128     // largest meta-model of sgp_ego_scan (include/sgp.h) = one SGP_TILE
+#endif
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -414,6 +417,31 @@ hipError_t launch_flap_gemv(const double* A, int64_t mp, const double* x, const 
 // s2_i = 1/2 (S_ii - sum_j T_ij S_ij) W3_i for i < n, else 0
 hipError_t launch_flap_rowdot(const double* S, const double* T, int64_t mp, int64_t n,
                               const double* W3, double* s2, hipStream_t s);
+
+// ---------------------------------------------------------------- k_ego.hip
+// The EGO proposal's expected-improvement scan (sgp_ego_scan): one pass over the n resident rows
+// X (column-major, ld ldx, zero padded to a multiple of 128 rows) against a meta-model of
+// T <= SGP_EGO_TMAX points.
+struct EgoScan {
+  const double* X;
+  int64_t ldx, n;
+  int d, T;
+  int kexp;                  // 1: "exp" (L1 distance), 0: "sqexp"
+  double coef, sig2;         // k = sig2 exp(coef * dist)
+  double c0, tau2;           // sigma^2 + tau^2, tau^2
+  double v1, vmax;           // vals[0], max vals
+  const double* xm;          // meta points, column-major, ld SGP_EGO_TMAX, zero padded rows
+  const double* Ainv;        // K22^-1, SGP_EGO_TMAX x SGP_EGO_TMAX, row-major
+  const double* alpha;       // K22^-1 (v - v1), SGP_EGO_TMAX values, zero padded
+  const double* ex;          // excluded rows, E x d column-major (ld E), sorted by coordinate 0
+  int64_t E;
+  double *ei_out, *mean_out, *var_out;   // n values each, or nullptr
+  double* rec;               // 2 doubles per workgroup (max_blocks of them)
+};
+// status: the K22 chain's status word; out (3 doubles): the winner's EI, its row (-1: every row
+// excluded) and *status, written by the one-block final reduction
+hipError_t launch_ego_scan(const EgoScan& a, int max_blocks, const int* status, double* out,
+                           hipStream_t s);
 
 // knot gradients (k_mfma.hip / k_cov.hip)
 // out[j*d + c] (+)= sum over row tiles of knot_slab (deterministic two-level reduction);

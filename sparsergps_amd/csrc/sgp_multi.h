@@ -21,6 +21,11 @@ hipStream_t sgp_internal_stream(sgp_ctx* c);  // the context's launch stream
 int sgp_internal_share_streams(sgp_ctx* c, sgp_ctx* src);   // c uses src's three streams
 int sgp_internal_check_bernoulli_y(const double* y, int64_t n, int64_t row0);   // all in {0, 1}
 int sgp_internal_lap_set_family(sgp_ctx* c, int family, int64_t row0);
+// sgp_ego_scan on one shard (arguments already checked); *best_row = -1: every row excluded
+int sgp_internal_ego_scan(sgp_ctx* c, int kernel, const double* theta, double delta,
+                          const double* xm, int64_t T, int64_t ldxm, const double* vals,
+                          const double* excl, int64_t E, int64_t ldexcl, int64_t* best_row,
+                          double* best_ei, double* ei_out, double* mean_out, double* var_out);
 
 int multi_create(MultiCtx** out, const int* devices, int nshards, const double* X, int64_t n,
                  int64_t ldx, int d, const double* y, const double* mu, int64_t m_max);
@@ -41,6 +46,11 @@ int multi_lap_set_expo(MultiCtx* mc, const double* a, double fill);
 int multi_lap_set_family(MultiCtx* mc, int family);
 int multi_lap_get_f(MultiCtx* mc, double* f);
 int multi_lap_get_grad_psi(MultiCtx* mc, double* out);
+// rows and the optional n-vectors in the global row order; *best_row = -1: every row excluded
+int multi_ego_scan(MultiCtx* mc, int kernel, const double* theta, double delta, const double* xm,
+                   int64_t T, int64_t ldxm, const double* vals, const double* excl, int64_t E,
+                   int64_t ldexcl, int64_t* best_row, double* best_ei, double* ei_out,
+                   double* mean_out, double* var_out);
 int multi_enable_knot_grad(MultiCtx* mc, int enable);
 int multi_knot_gradient(MultiCtx* mc, const double* bounds, double* grad_knot);
 int multi_row_bounds(MultiCtx* mc, double* lo, double* hi);

@@ -373,6 +373,44 @@ class SparseGPContext:
                                                 int(maxit), _lib.dptr(Cd), T, T, _lib.dptr(out)))
         return out
 
+    def ego_scan(self, ego_cov_par, ego_cov_fun, xm, vals, excl=None, delta=1e-6,
+                 want=("ei", "mean", "var")):
+        """The EGO proposals' expected-improvement scan over this context's rows (sgp_ego_scan;
+        R/vi_functions.R:1927-1950): meta-model points ``xm`` (T x d, T <= 128) with objective
+        values ``vals``, meta covariance ``ego_cov_par`` = {sigma, l, tau} (or [sigma, l, tau])
+        of kind ``ego_cov_fun`` ("exp" or "sqexp"), rows equal to a row of ``excl`` (the knots)
+        left out.  ``delta`` is the caller's delta: the reference's delta / 1000 goes to the
+        meta-model's diagonal.  Returns a dict with ``row`` (0-based, R's which.max(EI)),
+        ``best_ei`` (its EI) and, for each name in ``want``, the n-vector: "ei" (NaN on excluded
+        rows), "mean", "var"."""
+        if ego_cov_fun not in ("exp", "sqexp"):
+            raise ValueError(f"ego_cov_fun must be 'exp' or 'sqexp', not {ego_cov_fun!r}")
+        if isinstance(ego_cov_par, dict):
+            th = np.array([ego_cov_par["sigma"], ego_cov_par["l"], ego_cov_par["tau"]],
+                          dtype=np.float64)
+        else:
+            th = np.ascontiguousarray(np.asarray(ego_cov_par, dtype=np.float64).reshape(3))
+        bad = set(want) - {"ei", "mean", "var"}
+        if bad:
+            raise ValueError(f"want: unknown vector(s) {sorted(bad)}")
+        Xm = np.asfortranarray(np.asarray(xm, dtype=np.float64).reshape(-1, self.d))
+        T = Xm.shape[0]
+        v = np.ascontiguousarray(np.asarray(vals, dtype=np.float64).reshape(-1))
+        if v.size != T:
+            raise ValueError(f"{v.size} objective values for {T} meta-model points")
+        Ex, E = None, 0
+        if excl is not None:
+            Ex = np.asfortranarray(np.asarray(excl, dtype=np.float64).reshape(-1, self.d))
+            E = Ex.shape[0]
+        vecs = {k: np.zeros(self.n, dtype=np.float64) for k in ("ei", "mean", "var") if k in want}
+        row, ei = C.c_int64(-1), C.c_double(0.0)
+        _lib.check(self._lib.sgp_ego_scan(
+            self.handle, _lib.KERNELS[ego_cov_fun], _lib.dptr(th), float(delta) / 1000.0,
+            _lib.dptr(Xm), T, T, _lib.dptr(v), None if Ex is None else _lib.dptr(Ex), E, max(E, 1),
+            C.byref(row), C.byref(ei), *(None if k not in vecs else _lib.dptr(vecs[k])
+                                         for k in ("ei", "mean", "var"))))
+        return {"row": int(row.value), "best_ei": float(ei.value), **vecs}
+
     def lap_nr(self, theta, cov_fun, xu, delta=1e-6, expo=1.0, tol=1e-5, maxit=1000):
         """newtrap_sparseGP alone from the resident f: (last objective value, NR iterations);
         f is left at the mode."""
