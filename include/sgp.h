@@ -223,7 +223,8 @@ int sgp_lap_set_expo(sgp_ctx* ctx, const double* a /* n host values, or NULL */,
  * starts NR at f = 0 (R/optimize_gp.R:583).  Every response must be 0 or 1: SGP_EINVAL names the
  * first that is not, checked here and whenever sgp_ctx_set_data replaces y under this family
  * (not per evaluation); the family is left as it was.  An unknown family is SGP_EINVAL. */
-enum { SGP_FAM_POISSON = 0, SGP_FAM_BERNOULLI = 1 };
+enum { SGP_FAM_POISSON = 0, SGP_FAM_BERNOULLI = 1,
+       SGP_FAM_GAUSSIAN = 2 /* sgp_nlp / sgp_predict_nlp only: sgp_lap_set_family refuses it */ };
 int sgp_lap_set_family(sgp_ctx* ctx, int family);
 int sgp_lap_get_f(sgp_ctx* ctx, double* f /* n host values */);
 /* grad psi of the last Newton-Raphson step (n host values): the `gradient` element
@@ -326,6 +327,45 @@ int sgp_predict(int device, int kernel, const double* theta, double delta, int m
                 const double* muu, const double* u_var, int64_t ldv, const double* x_pred,
                 int64_t np, int64_t ldxp, int d, const double* mu_pred, int full_cov,
                 double* pred_mean, double* pred_var, int64_t ldpv);
+
+/* Held-out scoring: the reference's my_nlp(mc = FALSE, mv = FALSE) (R/evaluation_functions.R:12-145)
+ * over n test rows -- nlp[i] = -log int p(y_i | f) N(f; pred_mean_i, pred_var_i) df:
+ *   SGP_FAM_GAUSSIAN   -dnorm(y, pred_mean, sqrt(pred_var + tau^2), log = TRUE) (l.14-20), par = tau;
+ *                      pred_var + tau^2 as written, although the sparse predictors' pred_var
+ *                      already holds tau^2
+ *   SGP_FAM_BERNOULLI  p = dbinom(y, 1, my_logistic(f)) (l.30-52); par is ignored
+ *   SGP_FAM_POISSON    p = dpois(y, exp(f) m) (l.84-110), par = the scalar exposure m > 0 (the
+ *                      reference's par$m), or expo = n per-row exposures (par is then not read)
+ * The reference calls R's integrate() once per row in a loop; here every row's integral is taken
+ * in one launch by a fixed rule accurate to fp64 rounding (mode, level set, 128-point midpoint
+ * rule in log space: DESIGN.md sec. 0j).  integrate()'s infinite-range rule misses narrow
+ * integrands and returns 0 (nlp = Inf), and its linear-space integrand underflows; neither is
+ * reproduced (quirks Q21, Q22).
+ * stats[4] = {sum of the finite nlp values, their count, the count of NaN rows,
+ * sum (pred_mean - y)^2}, each added in a fixed order (bit-identical on repeat).
+ * SGP_EINVAL before any device call for: a NULL pointer (expo may be NULL), n < 1, an unknown
+ * family, a non-finite y, a bernoulli y outside {0, 1}, a poisson y that is negative or not an
+ * integer (R: a warning and probability 0; quirk Q24), a poisson exposure that is not positive and
+ * finite, a gaussian tau that is not finite or < 0, expo given for another family than poisson.
+ * Data problems are not errors: a row whose pred_mean is not finite, or whose variance (gaussian:
+ * pred_var + tau^2) is not finite or <= 0, gets nlp = NaN and is counted in stats[2]; every other
+ * row is unaffected (the reference stops in integrate with "non-finite function value"). */
+int sgp_nlp(int device, int family, const double* y, const double* pred_mean,
+            const double* pred_var, int64_t n, double par, const double* expo, double* nlp,
+            double* stats /* 4 */);
+
+/* sgp_predict(..., full_cov = 0) followed by sgp_nlp of its result against y_pred (np values),
+ * as the reference's experiment scripts do (exec/boston.R:191-201, exec/airfoil.R:181-191,
+ * exec/ccpp.R:168-178), without the round trip: the prediction's device stages run as in
+ * sgp_predict, pred_mean and pred_var are formed and scored on the device, and the np-vectors are
+ * read back once.  pred_mean and pred_var are bit-identical to sgp_predict's and nlp / stats to
+ * sgp_nlp's on those vectors.  Arguments and errors as the two entries'. */
+int sgp_predict_nlp(int device, int kernel, const double* theta, double delta, int method,
+                    int gaussian, const double* U, int64_t m, int64_t ldu, const double* u_mean,
+                    const double* muu, const double* u_var, int64_t ldv, const double* x_pred,
+                    int64_t np, int64_t ldxp, int d, const double* mu_pred, double* pred_mean,
+                    double* pred_var, int family, const double* y_pred, double par,
+                    const double* expo, double* nlp, double* stats /* 4 */);
 
 /* Knot gradients (xu_opt = "simultaneous"; the knot branches of delbo_dcov_par
  * R/vi_functions.R:425-593, dlogp_dcov_par R/laplace_approx_gradient.R:973-1126 and

@@ -49,6 +49,13 @@ int sgp_diag_ego_args(int d, int kernel, const double* theta_meta, double delta_
                       const double* xm, int64_t T, int64_t ldxm, const double* vals,
                       const double* excl, int64_t E, int64_t ldexcl);
 
+/* sgp_nlp (sgp.h) with its grid exposed: max_blocks = the cap on the scoring kernel's workgroups
+ * (0 = the product's, eight per compute unit).  The result must not depend on it.  *kernel_ms
+ * (or NULL): the scoring launches alone, by HIP events, without the copies. */
+int sgp_diag_nlp(int device, int family, int max_blocks, const double* y,
+                 const double* pred_mean, const double* pred_var, int64_t n, double par,
+                 const double* expo, double* nlp, double* stats, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ from ._build import build
 from ._lib import NotPositiveDefinite, SGPError
 from .covariance import (cov_fun_expC, cov_fun_sqrd_exp_ardC, cov_fun_sqrd_expC, dsig_dtheta_ardC,
                          dsig_dthetaC, make_cov_mat_ardC, make_cov_matC)
+from .evaluation import my_kl, my_nlp, my_rmse, predict_prob, score_gp
 from .drivers import laplace_grad_ascent, norm_grad_ascent, norm_grad_ascent_vi
 from .full import (dlogp_dcov_par_full, dlogq_dcov_par_full, full_eval, full_laplace_eval,
                    laplace_grad_ascent_full, newtrapGP, norm_grad_ascent_full, obj_fun_bern_full,
@@ -32,4 +33,5 @@ __all__ = [
     "full_laplace_eval", "newtrapGP", "obj_fun_pois_full", "obj_fun_bern_full",
     "dlogq_dcov_par_full", "laplace_grad_ascent_full", "predict_laplace_full",
     "knot_prop_ego_norm_vi", "knot_prop_ego_norm", "knot_prop_ego",
+    "my_rmse", "my_nlp", "my_kl", "predict_prob", "score_gp",
 ]

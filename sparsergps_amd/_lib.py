@@ -24,6 +24,7 @@ SGP_FLAG_OBJ_ONLY = 2
 SGP_PRED_VI, SGP_PRED_LAPLACE, SGP_PRED_FULL, SGP_PRED_LAPLACE_FULL = 0, 1, 2, 3
 SGP_EXPO_ROWS = 0.0   # expo argument: the per-row exposure of sgp_lap_set_expo
 FAMILIES = {"poisson": 0, "bernoulli": 1}   # SGP_FAM_*: sgp_lap_set_family
+SCORE_FAMILIES = {**FAMILIES, "gaussian": 2}   # sgp_nlp / sgp_predict_nlp
 
 # name -> (restype, argtypes); exactly the functions declared in include/sgp.h
 PROTOTYPES = {
@@ -104,6 +105,16 @@ PROTOTYPES = {
                               C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int64,
                               c_double_p, C.c_int64, C.c_int64, C.c_int, c_double_p, C.c_int,
                               c_double_p, c_double_p, C.c_int64]),
+    "sgp_nlp": (C.c_int, [C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, C.c_int64,
+                          C.c_double, c_double_p, c_double_p, c_double_p]),
+    "sgp_diag_nlp": (C.c_int, [C.c_int, C.c_int, C.c_int, c_double_p, c_double_p,
+                               c_double_p, C.c_int64, C.c_double, c_double_p, c_double_p,
+                               c_double_p, c_double_p]),
+    "sgp_predict_nlp": (C.c_int, [C.c_int, C.c_int, c_double_p, C.c_double, C.c_int, C.c_int,
+                                  c_double_p, C.c_int64, C.c_int64, c_double_p, c_double_p,
+                                  c_double_p, C.c_int64, c_double_p, C.c_int64, C.c_int64, C.c_int,
+                                  c_double_p, c_double_p, c_double_p, C.c_int, c_double_p,
+                                  C.c_double, c_double_p, c_double_p, c_double_p]),
     "sgp_ctx_enable_knot_grad": (C.c_int, [C.c_void_p, C.c_int]),
     "sgp_knot_red_extra": (C.c_int64, [C.c_int, C.c_int64]),
     "sgp_knot_gradient": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),

@@ -3207,13 +3207,179 @@ struct IntBuf {
   int* p = nullptr;
   ~IntBuf() { if (p) (void)hipFree(p); }
 };
+
+// sgp_predict_nlp's scoring request (checked by nlp_check_args before predict_run is entered)
+struct PredScore {
+  int family;
+  const double* y;
+  double par;
+  const double* expo;
+  double* nlp;
+  double* stats;
+};
+
+bool is_finite(double v) { return fabs(v) <= 1.79769313486231570815e308; }
+
+// The argument checks of sgp_nlp / sgp_predict_nlp; no device call.
+int nlp_check_args(const char* who, int family, const double* y, int64_t n, double par,
+                   const double* expo, const double* nlp, const double* stats) {
+  if (!y || !nlp || !stats || n < 1) {
+    set_err("%s: NULL argument or n < 1", who);
+    return SGP_EINVAL;
+  }
+  if (family != SGP_FAM_POISSON && family != SGP_FAM_BERNOULLI && family != SGP_FAM_GAUSSIAN) {
+    set_err("%s: unknown family %d", who, family);
+    return SGP_EINVAL;
+  }
+  if (expo && family != SGP_FAM_POISSON) {
+    set_err("%s: a per-row exposure is for the poisson family only", who);
+    return SGP_EINVAL;
+  }
+  if (family == SGP_FAM_GAUSSIAN && !(is_finite(par) && par >= 0.0)) {
+    set_err("%s: gaussian tau = %g is not finite and >= 0", who, par);
+    return SGP_EINVAL;
+  }
+  if (family == SGP_FAM_POISSON && !expo && !(is_finite(par) && par > 0.0)) {
+    set_err("%s: poisson exposure m = %g is not positive and finite", who, par);
+    return SGP_EINVAL;
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    if (!is_finite(y[i])) {
+      set_err("%s: y[%lld] = %g is not finite", who, (long long)i, y[i]);
+      return SGP_EINVAL;
+    }
+    if (family == SGP_FAM_BERNOULLI && !(y[i] == 0.0 || y[i] == 1.0)) {
+      set_err("%s: bernoulli y[%lld] = %g is not 0 or 1", who, (long long)i, y[i]);
+      return SGP_EINVAL;
+    }
+    if (family == SGP_FAM_POISSON && !(y[i] >= 0.0 && y[i] == floor(y[i]))) {
+      set_err("%s: poisson y[%lld] = %g is not a non-negative integer", who, (long long)i, y[i]);
+      return SGP_EINVAL;
+    }
+    if (expo && !(is_finite(expo[i]) && expo[i] > 0.0)) {
+      set_err("%s: poisson exposure expo[%lld] = %g is not positive and finite", who,
+              (long long)i, expo[i]);
+      return SGP_EINVAL;
+    }
+  }
+  return SGP_OK;
+}
+
+// the scoring grid's cap: eight workgroups per compute unit
+int nlp_max_blocks(int device, int* out) {
+  int cus = 0;
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  *out = 8 * (cus > 0 ? cus : 1);
+  return SGP_OK;
+}
+
+// sgp_nlp's body.  max_blocks = 0: the product's; kernel_ms (or NULL): the two scoring launches'
+// time by HIP events (sgp_diag_nlp)
+int nlp_run(int device, int family, int max_blocks, const double* y,
+            const double* pred_mean, const double* pred_var, int64_t n, double par,
+            const double* expo, double* nlp, double* stats, double* kernel_ms) {
+  if (!pred_mean || !pred_var) {
+    set_err("sgp_nlp: NULL argument or n < 1");
+    return SGP_EINVAL;
+  }
+  int st = nlp_check_args("sgp_nlp", family, y, n, par, expo, nlp, stats);
+  if (st) return st;
+  if (max_blocks < 0) {
+    set_err("sgp_nlp: max_blocks < 0");
+    return SGP_EINVAL;
+  }
+  HIPCHK(hipSetDevice(device));
+  if (max_blocks == 0 && (st = nlp_max_blocks(device, &max_blocks))) return st;
+  StreamGuard sg;
+  HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+  hipStream_t s = sg.s;
+  DevBuf dy, dm, dv, de, dn, part, dst;
+  st = dalloc(&dy.p, n);
+  st = st ? st : dalloc(&dm.p, n);
+  st = st ? st : dalloc(&dv.p, n);
+  st = st ? st : dalloc(&dn.p, n);
+  st = st ? st : dalloc(&part.p, nlp_part_doubles(n));
+  st = st ? st : dalloc(&dst.p, 4);
+  if (!st && expo) st = dalloc(&de.p, n);
+  if (st) return st;
+  const size_t nb = sizeof(double) * (size_t)n;
+  HIPCHK(hipMemcpyAsync(dy.p, y, nb, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dm.p, pred_mean, nb, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dv.p, pred_var, nb, hipMemcpyHostToDevice, s));
+  if (expo) HIPCHK(hipMemcpyAsync(de.p, expo, nb, hipMemcpyHostToDevice, s));
+  NlpArgs a{dy.p, dm.p, dv.p, expo ? de.p : nullptr, par, n, dn.p, part.p};
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (kernel_ms) {
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventRecord(e0, s));
+  }
+  hipError_t le = launch_nlp_rows(family, a, max_blocks, dst.p, s);
+  if (kernel_ms && le == hipSuccess) le = hipEventRecord(e1, s);
+  if (le == hipSuccess) le = hipMemcpyAsync(nlp, dn.p, nb, hipMemcpyDeviceToHost, s);
+  if (le == hipSuccess) le = hipMemcpyAsync(stats, dst.p, sizeof(double) * 4, hipMemcpyDeviceToHost, s);
+  if (le == hipSuccess) le = hipStreamSynchronize(s);
+  if (kernel_ms) {
+    float ms = 0.0f;
+    if (le == hipSuccess) le = hipEventElapsedTime(&ms, e0, e1);
+    *kernel_ms = (double)ms;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+  HIPCHK(le);
+  return SGP_OK;
+}
+
+int predict_run(int device, int kernel, const double* theta, double delta, int method,
+                int gaussian, const double* U, int64_t m, int64_t ldu, const double* u_mean,
+                const double* muu, const double* u_var, int64_t ldv, const double* x_pred,
+                int64_t np, int64_t ldxp, int d, const double* mu_pred, int full_cov,
+                double* pred_mean, double* pred_var, int64_t ldpv, const PredScore* sc);
 }  // namespace
+
+int sgp_nlp(int device, int family, const double* y, const double* pred_mean,
+            const double* pred_var, int64_t n, double par, const double* expo, double* nlp,
+            double* stats) {
+  return nlp_run(device, family, 0, y, pred_mean, pred_var, n, par, expo, nlp, stats, nullptr);
+}
+
+int sgp_diag_nlp(int device, int family, int max_blocks, const double* y,
+                 const double* pred_mean, const double* pred_var, int64_t n, double par,
+                 const double* expo, double* nlp, double* stats, double* kernel_ms) {
+  return nlp_run(device, family, max_blocks, y, pred_mean, pred_var, n, par, expo, nlp, stats,
+                 kernel_ms);
+}
 
 int sgp_predict(int device, int kernel, const double* theta, double delta, int method,
                 int gaussian, const double* U, int64_t m, int64_t ldu, const double* u_mean,
                 const double* muu, const double* u_var, int64_t ldv, const double* x_pred,
                 int64_t np, int64_t ldxp, int d, const double* mu_pred, int full_cov,
                 double* pred_mean, double* pred_var, int64_t ldpv) {
+  return predict_run(device, kernel, theta, delta, method, gaussian, U, m, ldu, u_mean, muu, u_var,
+                     ldv, x_pred, np, ldxp, d, mu_pred, full_cov, pred_mean, pred_var, ldpv,
+                     nullptr);
+}
+
+int sgp_predict_nlp(int device, int kernel, const double* theta, double delta, int method,
+                    int gaussian, const double* U, int64_t m, int64_t ldu, const double* u_mean,
+                    const double* muu, const double* u_var, int64_t ldv, const double* x_pred,
+                    int64_t np, int64_t ldxp, int d, const double* mu_pred, double* pred_mean,
+                    double* pred_var, int family, const double* y_pred, double par,
+                    const double* expo, double* nlp, double* stats) {
+  int st = nlp_check_args("sgp_predict_nlp", family, y_pred, np, par, expo, nlp, stats);
+  if (st) return st;
+  const PredScore sc{family, y_pred, par, expo, nlp, stats};
+  return predict_run(device, kernel, theta, delta, method, gaussian, U, m, ldu, u_mean, muu, u_var,
+                     ldv, x_pred, np, ldxp, d, mu_pred, 0, pred_mean, pred_var, 0, &sc);
+}
+
+namespace {
+// sgp_predict (sc == nullptr) and sgp_predict_nlp (sc: score the prediction on the device)
+int predict_run(int device, int kernel, const double* theta, double delta, int method,
+                int gaussian, const double* U, int64_t m, int64_t ldu, const double* u_mean,
+                const double* muu, const double* u_var, int64_t ldv, const double* x_pred,
+                int64_t np, int64_t ldxp, int d, const double* mu_pred, int full_cov,
+                double* pred_mean, double* pred_var, int64_t ldpv, const PredScore* sc) {
   KernParams kp;
   int st = make_params(kernel, d, theta, delta, &kp);
   if (st) return st;
@@ -3334,9 +3500,49 @@ int sgp_predict(int device, int kernel, const double* theta, double delta, int m
   HIPCHK(launch_build_knm(kp, Xp.p, npp, np, npp, dU.p, mp, m, mp, Kp.p, s));
   HIPCHK(launch_gemv_rows(Kp.p, npp, mp, wv.p, nullptr, yv.p, nullptr, s));
   std::vector<double> hy((size_t)npp), hq((size_t)npp, 0.0);
+  // vi_functions.R:1321: tau^2 + sigma^2 + delta; laplace_approx_prediction.R:114: sigma^2 + tau^2
+  // predict_gp_full: diag(Sigma11) = sigma^2 + tau^2 + delta
+  const double c0 = (method == SGP_PRED_VI) ? (kp.tau2 + kp.sig2) + delta
+                                            : (full ? (kp.sig2 + kp.tau2) + delta
+                                                    : kp.sig2 + kp.tau2);
   if (!full_cov) {
     HIPCHK(launch_rowquad_knm(kp, Kp.p, T22.p, np, npp, m, mp, nullptr, 0.0, nullptr, nullptr,
                               nullptr, rowq.p, q.p, s));
+    if (sc) {
+      // pred_mean and pred_var formed and scored on the device; one readback of the np-vectors
+      int max_blocks = 0;
+      if ((st = nlp_max_blocks(device, &max_blocks))) return st;
+      DevBuf dmu, dy, de, dpm, dpv, dn, part, dst;
+      st = dalloc(&dmu.p, np);
+      st = st ? st : dalloc(&dy.p, np);
+      st = st ? st : dalloc(&dpm.p, np);
+      st = st ? st : dalloc(&dpv.p, np);
+      st = st ? st : dalloc(&dn.p, np);
+      st = st ? st : dalloc(&part.p, nlp_part_doubles(np));
+      st = st ? st : dalloc(&dst.p, 4);
+      if (!st && sc->expo) st = dalloc(&de.p, np);
+      if (st) return st;
+      const size_t nb = sizeof(double) * (size_t)np;
+      HIPCHK(hipMemcpyAsync(dmu.p, mu_pred, nb, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(dy.p, sc->y, nb, hipMemcpyHostToDevice, s));
+      if (sc->expo) HIPCHK(hipMemcpyAsync(de.p, sc->expo, nb, hipMemcpyHostToDevice, s));
+      HIPCHK(launch_pred_finish(dmu.p, yv.p, q.p, c0, np, dpm.p, dpv.p, s));
+      NlpArgs a{dy.p, dpm.p, dpv.p, sc->expo ? de.p : nullptr, sc->par, np, dn.p, part.p};
+      HIPCHK(launch_nlp_rows(sc->family, a, max_blocks, dst.p, s));
+      int hst[4];
+      HIPCHK(hipMemcpyAsync(pred_mean, dpm.p, nb, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(pred_var, dpv.p, nb, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(sc->nlp, dn.p, nb, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(sc->stats, dst.p, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(hst, status.p, sizeof(hst), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      if (hst[0]) {
+        set_err("%s is not positive definite (leading minor of order %d)",
+                lapfull ? "I + sqrt(-W) %*% Sigma %*% sqrt(-W)" : "Sigma22", hst[0]);
+        return SGP_ENOTPD;
+      }
+      return SGP_OK;
+    }
   } else {
     if (lap_full)
       HIPCHK(launch_rowquad_knm(kp, Kp.p, Kinv.p, np, npp, m, mp, nullptr, 0.0, nullptr, nullptr,
@@ -3362,11 +3568,6 @@ int sgp_predict(int device, int kernel, const double* theta, double delta, int m
   }
   for (int64_t i = 0; i < np; ++i) pred_mean[i] = mu_pred[i] + hy[(size_t)i];
   if (!full_cov) {
-    // vi_functions.R:1321: tau^2 + sigma^2 + delta; laplace_approx_prediction.R:114: sigma^2 + tau^2
-    // predict_gp_full: diag(Sigma11) = sigma^2 + tau^2 + delta
-    const double c0 = (method == SGP_PRED_VI) ? (kp.tau2 + kp.sig2) + delta
-                                              : (full ? (kp.sig2 + kp.tau2) + delta
-                                                      : kp.sig2 + kp.tau2);
     for (int64_t i = 0; i < np; ++i) pred_var[i] = c0 + hq[(size_t)i];
     return SGP_OK;
   }
@@ -3381,6 +3582,7 @@ int sgp_predict(int device, int kernel, const double* theta, double delta, int m
   }
   return SGP_OK;
 }
+}  // namespace
 
 
 // ------------------------------------------------------------------------- OAT candidates

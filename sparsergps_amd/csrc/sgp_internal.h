@@ -443,6 +443,27 @@ struct EgoScan {
 hipError_t launch_ego_scan(const EgoScan& a, int max_blocks, const int* status, double* out,
                            hipStream_t s);
 
+// ---------------------------------------------------------------- k_score.hip
+// Held-out scoring (sgp_nlp): nlp[i] = my_nlp's value for row i (sgp_quad.h) and, per tile of
+// 256 rows, four partials in part (nlp_part_doubles(n) doubles).
+struct NlpArgs {
+  const double *y, *pm, *pv;   // n values each: response, pred_mean, pred_var
+  const double* expo;          // n per-row poisson exposures, or nullptr: par on every row
+  double par;                  // gaussian: tau; poisson: the exposure
+  int64_t n;
+  double* nlp;                 // n values
+  double* part;
+};
+int64_t nlp_part_doubles(int64_t n);
+// fam: SGP_FAM_*.  stats (4 doubles, device): the sum
+// and the count of the finite nlp values, the count of NaN rows, sum (pred_mean - y)^2, added
+// over the tiles in tile order by a one-block kernel (independent of max_blocks).
+hipError_t launch_nlp_rows(int fam, const NlpArgs& a, int max_blocks, double* stats,
+                           hipStream_t s);
+// pm = mu_pred + yv, pv = c0 + q (np values): sgp_predict's two host sums, on the device
+hipError_t launch_pred_finish(const double* mu_pred, const double* yv, const double* q, double c0,
+                              int64_t np, double* pm, double* pv, hipStream_t s);
+
 // knot gradients (k_mfma.hip / k_cov.hip)
 // out[j*d + c] (+)= sum over row tiles of knot_slab (deterministic two-level reduction);
 // part: 64 * mp * d doubles of work space

@@ -22,7 +22,9 @@ from .vi import _device
 
 
 def _predict(method, gaussian, u_mean, u_var, xu, x_pred, cov_fun, cov_par, mu, muu, full_cov,
-             delta):
+             delta, score=None):
+    """score = (family, y_pred, par, expo) scores the prediction on the device as well
+    (sgp_predict_nlp; full_cov must be False) and adds "nlp" and "stats" to the result."""
     lib = _lib.lib()
     _lib.require_gpu()
     x_pred = np.asarray(x_pred, dtype=np.float64)
@@ -41,6 +43,26 @@ def _predict(method, gaussian, u_mean, u_var, xu, x_pred, cov_fun, cov_par, mu, 
     mu_p = np.ascontiguousarray(np.broadcast_to(np.asarray(mu, dtype=np.float64), (npred,)))
     pm = np.zeros(npred, dtype=np.float64)
     pv = np.zeros((npred, npred) if full_cov else npred, dtype=np.float64, order="F")
+    if score is not None:
+        if full_cov:
+            raise ValueError("scoring takes the per-row variance (full_cov = False)")
+        family, y_pred, par, expo = score
+        yp = np.ascontiguousarray(np.asarray(y_pred, dtype=np.float64).reshape(-1))
+        if yp.size != npred:
+            raise ValueError(f"y has {yp.size} values for {npred} prediction rows")
+        ex = None
+        if expo is not None:
+            ex = np.ascontiguousarray(np.broadcast_to(np.asarray(expo, dtype=np.float64),
+                                                      (npred,)))
+        nlp, stats = np.zeros(npred), np.zeros(4)
+        _lib.check(lib.sgp_predict_nlp(
+            _device(), _lib.KERNELS[cov_fun], _lib.dptr(theta), float(delta), method,
+            1 if gaussian else 0, _lib.dptr(U), m, m, _lib.dptr(um), _lib.dptr(mu_u),
+            None if uv is None else _lib.dptr(uv), m, _lib.dptr(xp), npred, npred, d,
+            _lib.dptr(mu_p), _lib.dptr(pm), _lib.dptr(pv), _lib.SCORE_FAMILIES[family],
+            _lib.dptr(yp), float(par), None if ex is None else _lib.dptr(ex), _lib.dptr(nlp),
+            _lib.dptr(stats)))
+        return {"pred_mean": pm.reshape(-1, 1), "pred_var": pv, "nlp": nlp, "stats": stats}
     _lib.check(lib.sgp_predict(_device(), _lib.KERNELS[cov_fun], _lib.dptr(theta), float(delta),
                                method, 1 if gaussian else 0, _lib.dptr(U), m, m, _lib.dptr(um),
                                _lib.dptr(mu_u), None if uv is None else _lib.dptr(uv), m,
