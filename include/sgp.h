@@ -444,6 +444,40 @@ int sgp_ego_scan(sgp_ctx* ctx, int kernel, const double* theta_meta, double delt
                  const double* excl, int64_t E, int64_t ldexcl, int64_t* best_row,
                  double* best_ei, double* ei_out, double* mean_out, double* var_out);
 
+/* The cheap knot proposals' scan (knot_prop_var / knot_prop_error,
+ * R/knot_proposal_functions.R:4-42): the reference predicts at every training row with
+ * predict_laplace(full_cov = FALSE) (R/laplace_approx_prediction.R:3-123; x_pred = xy, mu = the
+ * fit's mean) and takes which.max of the variance or of the error.  Here it is one pass over the
+ * context's resident rows and mean, for a fit with knots U (m x d, column-major, ld ldu), knot
+ * posterior u_mean / u_var (m x m, column-major, ld ldv) and knot prior mean muu:
+ *   K22    = Kuu + delta I when gaussian, else Kuu + (tau^2 + delta) I   (l.25-62)
+ *   w      = K22^-1 (u_mean - muu),   A = K22^-1 - K22^-1 u_var K22^-1
+ *   mean_i = mu_i + k_i^T w           (the cross covariance k_i carries no nugget)
+ *   var_i  = sigma^2 + tau^2 - k_i^T A k_i                                (l.114)
+ *   key_i  = var_i                        (SGP_SCAN_VAR)
+ *          = |exp(f_i) - exp(mean_i)|     (SGP_SCAN_ERROR; l.38, as written for every family)
+ *   best_row = which.max(key) over the rows not in excl: ties to the lowest row, a NaN never wins
+ * kernel: SGP_KERNEL_SQEXP or SGP_KERNEL_ARD (SGP_KERNEL_EXP is refused, as sgp_predict refuses
+ * it); theta as the evaluations take it ([sigma, l.., tau]) with sigma > 0, l > 0, tau >= 0;
+ * delta >= 0.  f: n host values, or NULL for the context's resident Laplace mode (what
+ * sgp_lap_get_f returns; SGP_EINVAL when no Laplace evaluation has run); read in
+ * SGP_SCAN_ERROR only.  excl (E x d column-major, ld ldexcl, or NULL): as sgp_ego_scan's -- a row
+ * is excluded when all d of its coordinates equal (==) those of some row of excl.  The reference
+ * excludes nothing: excl = NULL is the parity setting.  best_row: 0-based row of the context's X;
+ * best_key: its key.  key_out / mean_out / var_out: n host values each or NULL -- key with NaN on
+ * the excluded rows.
+ * 1 <= m <= SGP_EGO_TMAX.  SGP_EINVAL before any device call for NULL arguments, m, a leading
+ * dimension or mode out of range, non-finite theta / U / u_mean / muu / u_var, sigma <= 0,
+ * l <= 0, tau < 0 or delta < 0; SGP_EINVAL for a multi-device context and when every row is
+ * excluded; SGP_ENOTPD naming "scan K22" when K22 is not positive definite.  A completed
+ * evaluation is left as it was (sgp_posterior_u still answers for it).  Bit-identical on repeat. */
+enum { SGP_SCAN_VAR = 0, SGP_SCAN_ERROR = 1 };
+int sgp_fit_scan(sgp_ctx* ctx, int kernel, const double* theta, double delta, int gaussian,
+                 const double* U, int64_t m, int64_t ldu, const double* u_mean, const double* muu,
+                 const double* u_var, int64_t ldv, int mode, const double* f,
+                 const double* excl, int64_t E, int64_t ldexcl, int64_t* best_row, double* best_key,
+                 double* key_out, double* mean_out, double* var_out);
+
 /* Per-phase timing (HIP events on the launch stream).  Enabling clears the record; every
  * evaluation after it appends its phases, and sgp_ctx_timings returns the per-phase totals
  * over those sgp_ctx_timing_evals() evaluations (names: '\n'-separated phase names; ms: their

@@ -49,6 +49,14 @@ int sgp_diag_ego_args(int d, int kernel, const double* theta_meta, double delta_
                       const double* xm, int64_t T, int64_t ldxm, const double* vals,
                       const double* excl, int64_t E, int64_t ldexcl);
 
+/* Host only (no device is touched): the argument checks sgp_fit_scan (sgp.h) runs before its
+ * first device call, for rows of dimension d -- the very function it calls.  SGP_OK or SGP_EINVAL
+ * with sgp_last_error(). */
+int sgp_diag_fit_scan_args(int d, int kernel, const double* theta, double delta, const double* U,
+                           int64_t m, int64_t ldu, const double* u_mean, const double* muu,
+                           const double* u_var, int64_t ldv, int mode, const double* excl,
+                           int64_t E, int64_t ldexcl);
+
 /* sgp_nlp (sgp.h) with its grid exposed: max_blocks = the cap on the scoring kernel's workgroups
  * (0 = the product's, eight per compute unit).  The result must not depend on it.  *kernel_ms
  * (or NULL): the scoring launches alone, by HIP events, without the copies. */

@@ -12,10 +12,15 @@ from .drivers import laplace_grad_ascent, norm_grad_ascent, norm_grad_ascent_vi
 from .full import (dlogp_dcov_par_full, dlogq_dcov_par_full, full_eval, full_laplace_eval,
                    laplace_grad_ascent_full, newtrapGP, norm_grad_ascent_full, obj_fun_bern_full,
                    obj_fun_norm_full, obj_fun_pois_full, predict_gp_full, predict_laplace_full)
+from .optimize import optimize_gp
 from .predict import predict_gp, predict_laplace, predict_vi
 from .laplace import (dlogq_dcov_par, laplace_eval, newtrap_sparseGP, obj_fun_bern,
                       obj_fun_pois)
-from .proposals import knot_prop_ego, knot_prop_ego_norm, knot_prop_ego_norm_vi
+from .knot_selection import (oat_knot_selection, oat_knot_selection_norm,
+                             oat_knot_selection_norm_vi)
+from .proposals import (knot_prop_ego, knot_prop_ego_norm, knot_prop_ego_norm_vi, knot_prop_error,
+                        knot_prop_random, knot_prop_random_norm, knot_prop_random_norm_vi,
+                        knot_prop_var)
 from .vi import (SparseGPContext, delbo_dcov_par, dlogp_dcov_par, elbo_fun, fitc_eval, param_names,
                  vi_eval)
 
@@ -33,5 +38,9 @@ __all__ = [
     "full_laplace_eval", "newtrapGP", "obj_fun_pois_full", "obj_fun_bern_full",
     "dlogq_dcov_par_full", "laplace_grad_ascent_full", "predict_laplace_full",
     "knot_prop_ego_norm_vi", "knot_prop_ego_norm", "knot_prop_ego",
+    "knot_prop_random_norm_vi", "knot_prop_random_norm", "knot_prop_random",
+    "knot_prop_var", "knot_prop_error",
+    "oat_knot_selection_norm_vi", "oat_knot_selection_norm", "oat_knot_selection",
+    "optimize_gp",
     "my_rmse", "my_nlp", "my_kl", "predict_prob", "score_gp",
 ]

@@ -22,7 +22,9 @@ KERNELS = {"sqexp": 0, "ard": 1, "exp": 2}
 SGP_FLAG_R_DET = 1
 SGP_FLAG_OBJ_ONLY = 2
 SGP_PRED_VI, SGP_PRED_LAPLACE, SGP_PRED_FULL, SGP_PRED_LAPLACE_FULL = 0, 1, 2, 3
-SGP_EXPO_ROWS = 0.0   # expo argument: the per-row exposure of sgp_lap_set_expo
+SGP_SCAN_VAR, SGP_SCAN_ERROR = 0, 1
+SGP_EGO_TMAX = 128    # sgp_ego_scan's T and sgp_fit_scan's m
+SGP_EXPO_ROWS = 0.0  # expo argument: the per-row exposure of sgp_lap_set_expo
 FAMILIES = {"poisson": 0, "bernoulli": 1}   # SGP_FAM_*: sgp_lap_set_family
 SCORE_FAMILIES = {**FAMILIES, "gaussian": 2}   # sgp_nlp / sgp_predict_nlp
 
@@ -132,6 +134,14 @@ PROTOTYPES = {
                                C.c_int64, c_double_p, c_double_p, C.c_int64, C.c_int64,
                                C.POINTER(C.c_int64), c_double_p, c_double_p, c_double_p,
                                c_double_p]),
+    "sgp_fit_scan": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_double, C.c_int, c_double_p,
+                               C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int64,
+                               C.c_int, c_double_p, c_double_p, C.c_int64, C.c_int64,
+                               C.POINTER(C.c_int64), c_double_p, c_double_p, c_double_p,
+                               c_double_p]),
+    "sgp_diag_fit_scan_args": (C.c_int, [C.c_int, C.c_int, c_double_p, C.c_double, c_double_p,
+                                         C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                         C.c_int64, C.c_int, c_double_p, C.c_int64, C.c_int64]),
     "sgp_ctx_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "sgp_ctx_timing_filter": (C.c_int, [C.c_void_p, C.c_char_p]),
     "sgp_ctx_timing_evals": (C.c_int64, [C.c_void_p]),

@@ -329,6 +329,9 @@ struct sgp_ctx {
   double* ego_ex = nullptr;
   int64_t ego_ex_cap = 0;
   int ego_blocks = 0;                     // workgroups of the scan: 8 per CU
+  // sgp_fit_scan: its own m x m work space and per-row f (SCAN_* offsets) beside the EGO scan's
+  // (knots, K22, its inverse, the chain's scratch, records), allocated on first use
+  double* scan = nullptr;
   // timing
   bool timing = false;
   std::string timing_only;                // record only the scopes of this name ("" = all)
@@ -531,7 +534,7 @@ void ctx_free(sgp_ctx* c) {
                   c->Cprev,  c->lapAZ,  c->lapAB,  c->laprv,  c->fl,
                   c->knot_slab, c->knot_part, c->knot_kmm, c->tslab, c->tq, c->tp,
                   c->rr_dev, c->Sfull, c->gjs, c->mmpart, c->rsync,
-                  c->ego,    c->ego_sync, c->ego_status, c->ego_rows, c->ego_ex};
+                  c->ego,    c->ego_sync, c->ego_status, c->ego_rows, c->ego_ex, c->scan};
   for (void* p : ptrs)
     if (p) hipFree(p);
   if (c->khash) hipFree(c->khash);
@@ -3183,6 +3186,268 @@ int sgp_ego_scan(sgp_ctx* c, int kernel, const double* theta_meta, double delta_
   if (st) return st;
   if (*best_row < 0) {
     set_err("sgp_ego_scan: no data row outside the knots (every row is excluded)");
+    return SGP_EINVAL;
+  }
+  return SGP_OK;
+}
+
+// ------------------------------------------------------------------------- fit scan
+// The predictive variance / error scan of knot_prop_var and knot_prop_error (include/sgp.h;
+// k_scan.hip): predict_laplace(full_cov = FALSE) at the context's own rows, and the arg-max.
+namespace {
+// c->scan (doubles): u_var | K22^-1 u_var | K22^-1 u_var K22^-1 | A | the d scales | f (n_pad)
+constexpr int64_t SCAN_V = 0, SCAN_T1 = SCAN_V + EGO_TT, SCAN_T22 = SCAN_T1 + EGO_TT,
+                  SCAN_A = SCAN_T22 + EGO_TT, SCAN_RL = SCAN_A + EGO_TT,
+                  SCAN_F = SCAN_RL + SGP_MAXD;
+
+int scan_check_args(int d, int kernel, const double* theta, double delta, const double* U,
+                    int64_t m, int64_t ldu, const double* u_mean, const double* muu,
+                    const double* u_var, int64_t ldv, int mode, const double* excl, int64_t E,
+                    int64_t ldexcl) {
+  if (kernel == SGP_KERNEL_EXP) {   // as sgp_predict: no fit carries it (optimize_gp.R:263)
+    set_err("sgp_fit_scan supports 'sqexp' and 'ard', as prediction does");
+    return SGP_EINVAL;
+  }
+  if (kernel != SGP_KERNEL_SQEXP && kernel != SGP_KERNEL_ARD) {
+    set_err("invalid covariance function (kernel=%d)", kernel);
+    return SGP_EINVAL;
+  }
+  if (d < 1 || d > SGP_MAXD) {
+    set_err("input dimension d=%d outside [1, %d]", d, SGP_MAXD);
+    return SGP_EINVAL;
+  }
+  if (!theta || !U || !u_mean || !muu || !u_var) {
+    set_err("sgp_fit_scan: theta, U, u_mean, muu and u_var must not be NULL");
+    return SGP_EINVAL;
+  }
+  if (mode != SGP_SCAN_VAR && mode != SGP_SCAN_ERROR) {
+    set_err("sgp_fit_scan: mode=%d is neither SGP_SCAN_VAR nor SGP_SCAN_ERROR", mode);
+    return SGP_EINVAL;
+  }
+  if (m < 1 || m > SGP_EGO_TMAX) {
+    set_err("sgp_fit_scan: m=%lld outside [1, %d]", (long long)m, SGP_EGO_TMAX);
+    return SGP_EINVAL;
+  }
+  if (ldu < m) {
+    set_err("sgp_fit_scan: ldu=%lld < m=%lld", (long long)ldu, (long long)m);
+    return SGP_EINVAL;
+  }
+  if (ldv < m) {
+    set_err("sgp_fit_scan: ldv=%lld < m=%lld", (long long)ldv, (long long)m);
+    return SGP_EINVAL;
+  }
+  if (excl && (E < 0 || ldexcl < E)) {
+    set_err("sgp_fit_scan: invalid exclusion list (E=%lld, ldexcl=%lld)", (long long)E,
+            (long long)ldexcl);
+    return SGP_EINVAL;
+  }
+  const int L = num_ls(kernel, d);
+  for (int p = 0; p < L + 2; ++p)
+    if (!std::isfinite(theta[p])) {
+      set_err("sgp_fit_scan: theta[%d] is not finite", p);
+      return SGP_EINVAL;
+    }
+  if (!(theta[0] > 0.0) || !(theta[L + 1] >= 0.0)) {
+    set_err("sgp_fit_scan: needs sigma > 0 and tau >= 0 (sigma=%g, tau=%g)", theta[0],
+            theta[L + 1]);
+    return SGP_EINVAL;
+  }
+  for (int p = 0; p < L; ++p)
+    if (!(theta[1 + p] > 0.0)) {
+      set_err("sgp_fit_scan: needs l > 0 (length scale %d is %g)", p + 1, theta[1 + p]);
+      return SGP_EINVAL;
+    }
+  if (!(delta >= 0.0) || !std::isfinite(delta)) {
+    set_err("sgp_fit_scan: delta=%g is not a finite value >= 0", delta);
+    return SGP_EINVAL;
+  }
+  for (int64_t j = 0; j < m; ++j) {
+    if (!std::isfinite(u_mean[j])) {
+      set_err("sgp_fit_scan: u_mean[%lld] is not finite", (long long)j);
+      return SGP_EINVAL;
+    }
+    if (!std::isfinite(muu[j])) {
+      set_err("sgp_fit_scan: muu[%lld] is not finite", (long long)j);
+      return SGP_EINVAL;
+    }
+  }
+  for (int q = 0; q < d; ++q)
+    for (int64_t j = 0; j < m; ++j)
+      if (!std::isfinite(U[j + q * ldu])) {
+        set_err("sgp_fit_scan: U[%lld, %d] is not finite", (long long)j, q);
+        return SGP_EINVAL;
+      }
+  for (int64_t k = 0; k < m; ++k)
+    for (int64_t j = 0; j < m; ++j)
+      if (!std::isfinite(u_var[j + k * ldv])) {
+        set_err("sgp_fit_scan: u_var[%lld, %lld] is not finite", (long long)j, (long long)k);
+        return SGP_EINVAL;
+      }
+  return SGP_OK;
+}
+
+int fit_scan_run(sgp_ctx* c, int kernel, const double* theta, double delta, int gaussian,
+                 const double* U, int64_t m, int64_t ldu, const double* u_mean, const double* muu,
+                 const double* u_var, int64_t ldv, int mode, const double* f, const double* excl,
+                 int64_t E, int64_t ldexcl, int64_t* best_row, double* best_key, double* key_out,
+                 double* mean_out, double* var_out) {
+  KernParams kp;
+  int st = make_params(kernel, c->d, theta, delta, &kp);
+  if (st) return st;
+  const int d = c->d;
+  constexpr int64_t TM = SGP_EGO_TMAX;
+  const bool resident_f = mode == SGP_SCAN_ERROR && !f;
+  if (resident_f && (!c->lv || c->lap_objs.empty())) {
+    set_err("sgp_fit_scan: f is NULL and no Laplace evaluation has run on this context");
+    return SGP_EINVAL;
+  }
+  // exclusion list: the rows that can match something (no NaN), sorted by coordinate 0
+  std::vector<double> hex;
+  int64_t Ex = 0;
+  if (excl && E > 0) {
+    std::vector<int64_t> idx;
+    for (int64_t k = 0; k < E; ++k) {
+      bool ok = true;
+      for (int q = 0; q < d && ok; ++q) ok = !std::isnan(excl[k + q * ldexcl]);
+      if (ok) idx.push_back(k);
+    }
+    std::stable_sort(idx.begin(), idx.end(),
+                     [&](int64_t a, int64_t b) { return excl[a] < excl[b]; });
+    Ex = (int64_t)idx.size();
+    hex.resize((size_t)(Ex * d));
+    for (int q = 0; q < d; ++q)
+      for (int64_t k = 0; k < Ex; ++k) hex[(size_t)(k + q * Ex)] = excl[idx[(size_t)k] + q * ldexcl];
+  }
+  HIPCHK(hipSetDevice(c->device));
+  st = ego_ensure(c, Ex);
+  if (st) return st;
+  if (!c->scan) {
+    st = dalloc(&c->scan, SCAN_F + c->n_pad);
+    if (st) return st;
+  }
+  hipStream_t s = c->stream;
+  std::vector<double> hxu((size_t)(TM * d), 0.0), hd((size_t)TM, 0.0), hV((size_t)EGO_TT, 0.0),
+      hrl((size_t)SGP_MAXD, 1.0);
+  for (int q = 0; q < d; ++q)
+    for (int64_t j = 0; j < m; ++j) hxu[(size_t)(q * TM + j)] = U[j + q * ldu];
+  for (int64_t j = 0; j < m; ++j) hd[(size_t)j] = u_mean[j] - muu[j];
+  for (int64_t i = 0; i < m; ++i)
+    for (int64_t j = 0; j < m; ++j) hV[(size_t)(i * TM + j)] = u_var[i + j * ldv];
+  if (kernel == SGP_KERNEL_ARD)
+    for (int q = 0; q < d; ++q) hrl[(size_t)q] = kp.rl[q];
+  double* w = c->ego;
+  double* w2 = c->scan;
+  timers_reset(c);
+  {
+    Scope sc(c, "scan_mm");   // uploads, K22, its inverse, w and A
+    // (the host buffers outlive the copies: every path below synchronises the stream or fails)
+    HIPCHK(hipMemcpyAsync(w + EGO_XM, hxu.data(), sizeof(double) * hxu.size(),
+                          hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(w + EGO_VEC, hd.data(), sizeof(double) * TM, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(w2 + SCAN_V, hV.data(), sizeof(double) * EGO_TT, hipMemcpyHostToDevice,
+                          s));
+    HIPCHK(hipMemcpyAsync(w2 + SCAN_RL, hrl.data(), sizeof(double) * SGP_MAXD,
+                          hipMemcpyHostToDevice, s));
+    if (mode == SGP_SCAN_ERROR && f)
+      HIPCHK(hipMemcpyAsync(w2 + SCAN_F, f, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice,
+                            s));
+    if (Ex > 0)
+      HIPCHK(hipMemcpyAsync(c->ego_ex, hex.data(), sizeof(double) * hex.size(),
+                            hipMemcpyHostToDevice, s));
+    // the chain's sync words must be zero when it starts (a failed chain may leave them set):
+    // zeroed on the launch stream, which a null-stream hipMemset would not be ordered with
+    HIPCHK(hipMemsetAsync(c->ego_status, 0, sizeof(int) * 4, s));
+    HIPCHK(hipMemsetAsync(c->ego_sync, 0, sizeof(unsigned) * SGP_GJ_SYNC_WORDS, s));
+    // K22 = Kuu + delta I (gaussian: the tau^2 I is subtracted again) or Kuu + (tau^2 + delta) I
+    // (laplace_approx_prediction.R:25-62), padded to the tile with a unit diagonal
+    HIPCHK(launch_build_kmm(kp, w + EGO_XM, TM, m, TM, gaussian ? kp.tau2 : 0.0, w + EGO_K22, s,
+                            w + EGO_INV));
+    HIPCHK(dense_spd_inverse(w + EGO_INV, TM, w + EGO_R, w + EGO_P, w + EGO_LOGD, c->ego_status,
+                             c->ego_sync, s));
+    HIPCHK(dense_gemv(w + EGO_INV, TM, w + EGO_VEC, 1.0, w + EGO_ALPHA, s));
+    HIPCHK(launch_gemm64(false, false, false, TM, TM, TM, 1.0, w + EGO_INV, TM, w2 + SCAN_V, TM,
+                         0.0, w2 + SCAN_T1, TM, s));
+    HIPCHK(launch_gemm64(false, false, false, TM, TM, TM, 1.0, w2 + SCAN_T1, TM, w + EGO_INV, TM,
+                         0.0, w2 + SCAN_T22, TM, s));
+    HIPCHK(dense_axpby(1.0, w + EGO_INV, -1.0, w2 + SCAN_T22, w2 + SCAN_A, EGO_TT, s));
+  }
+  FitScan a;
+  a.X = c->X;
+  a.ldx = c->n_pad;
+  a.n = c->n;
+  a.d = d;
+  a.m = (int)m;
+  a.mode = mode;
+  a.coef = kp.coef;
+  a.sig2 = kp.sig2;
+  a.c0 = kp.sig2 + kp.tau2;
+  a.rl = w2 + SCAN_RL;
+  a.mu = c->mu;
+  a.f = mode == SGP_SCAN_ERROR ? (resident_f ? lvec(c, LV_F) : w2 + SCAN_F) : nullptr;
+  a.xu = w + EGO_XM;
+  a.A = w2 + SCAN_A;
+  a.w = w + EGO_ALPHA;
+  a.ex = c->ego_ex;
+  a.E = Ex;
+  a.key_out = key_out ? c->ego_rows : nullptr;
+  a.mean_out = mean_out ? c->ego_rows + c->n_pad : nullptr;
+  a.var_out = var_out ? c->ego_rows + 2 * c->n_pad : nullptr;
+  a.rec = w + EGO_REC;
+  {
+    Scope sc(c, "fit_scan");   // the pass over X and its one-block final reduction
+    HIPCHK(launch_fit_scan(a, c->ego_blocks, c->ego_status, w + EGO_OUT, s));
+  }
+  double ho[3] = {0.0, -1.0, 0.0};
+  HIPCHK(hipMemcpyAsync(ho, w + EGO_OUT, sizeof(ho), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (ho[2] < 0.0) {
+    set_err("internal error: a Gauss-Jordan chain's wait watchdog expired");
+    return SGP_EHIP;
+  }
+  if (ho[2] != 0.0) {
+    set_err("scan K22 is not positive definite (leading minor of order %d)", (int)ho[2]);
+    return SGP_ENOTPD;
+  }
+  const size_t nb = sizeof(double) * (size_t)c->n;
+  if (key_out) HIPCHK(hipMemcpyAsync(key_out, a.key_out, nb, hipMemcpyDeviceToHost, s));
+  if (mean_out) HIPCHK(hipMemcpyAsync(mean_out, a.mean_out, nb, hipMemcpyDeviceToHost, s));
+  if (var_out) HIPCHK(hipMemcpyAsync(var_out, a.var_out, nb, hipMemcpyDeviceToHost, s));
+  if (key_out || mean_out || var_out) HIPCHK(hipStreamSynchronize(s));
+  *best_row = (int64_t)ho[1];
+  *best_key = ho[0];
+  return SGP_OK;
+}
+}  // namespace
+
+int sgp_diag_fit_scan_args(int d, int kernel, const double* theta, double delta, const double* U,
+                           int64_t m, int64_t ldu, const double* u_mean, const double* muu,
+                           const double* u_var, int64_t ldv, int mode, const double* excl,
+                           int64_t E, int64_t ldexcl) {
+  return scan_check_args(d, kernel, theta, delta, U, m, ldu, u_mean, muu, u_var, ldv, mode, excl,
+                         E, ldexcl);
+}
+
+int sgp_fit_scan(sgp_ctx* c, int kernel, const double* theta, double delta, int gaussian,
+                 const double* U, int64_t m, int64_t ldu, const double* u_mean, const double* muu,
+                 const double* u_var, int64_t ldv, int mode, const double* f, const double* excl,
+                 int64_t E, int64_t ldexcl, int64_t* best_row, double* best_key, double* key_out,
+                 double* mean_out, double* var_out) {
+  if (!c || !best_row || !best_key) {
+    set_err("sgp_fit_scan: ctx, best_row and best_key must not be NULL");
+    return SGP_EINVAL;
+  }
+  int st = scan_check_args(c->d, kernel, theta, delta, U, m, ldu, u_mean, muu, u_var, ldv, mode,
+                           excl, E, ldexcl);
+  if (st) return st;
+  if (c->multi) {
+    set_err("sgp_fit_scan: multi-device contexts are not supported (predict at the rows instead)");
+    return SGP_EINVAL;
+  }
+  st = fit_scan_run(c, kernel, theta, delta, gaussian, U, m, ldu, u_mean, muu, u_var, ldv, mode, f,
+                    excl, E, ldexcl, best_row, best_key, key_out, mean_out, var_out);
+  if (st) return st;
+  if (*best_row < 0) {
+    set_err("sgp_fit_scan: every row is excluded");
     return SGP_EINVAL;
   }
   return SGP_OK;

@@ -23,33 +23,12 @@
 // grid.  No atomics.
 #include <math.h>
 
+#include "sgp_argmax.h"
 #include "sgp_internal.h"
 
 namespace {
 
 constexpr int EGO_ROWS = 64;   // rows per workgroup step: 4 waves x 16
-
-// a beats b: b empty, or a's key larger, or equal keys and a's row lower (R's which.max)
-__device__ __forceinline__ bool ego_better(double ka, double ra, double kb, double rb) {
-  if (rb < 0.0) return ra >= 0.0;
-  if (ra < 0.0) return false;
-  return ka > kb || (ka == kb && ra < rb);
-}
-
-// (key, row) maximum over the 256 threads; red: 8 doubles of LDS.  Valid in thread 0.
-__device__ __forceinline__ void ego_block_max(double& key, double& row, double* red) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const double k2 = __shfl_xor(key, off, 64), r2 = __shfl_xor(row, off, 64);
-    if (ego_better(k2, r2, key, row)) { key = k2; row = r2; }
-  }
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[2 * wv] = key; red[2 * wv + 1] = row; }
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < 4; ++w)
-      if (ego_better(red[2 * w], red[2 * w + 1], key, row)) { key = red[2 * w]; row = red[2 * w + 1]; }
-}
 
 // NT = Tp / 16 column blocks of the padded meta-model; ALDS: A staged in LDS (else read through
 // L1 / L2 from its 128 x 128 home)
@@ -154,21 +133,7 @@ __global__ void __launch_bounds__(256) k_ego_scan(EgoScan a, int ntiles) {
         ei = sd * (z * (0.5 * erfc(-z * 0.70710678118654752440)) +
                    0.39894228040143267794 * exp(-0.5 * z * z));
       }
-      bool excluded = false;
-      if (a.E > 0) {
-        const double x0 = xr[0];
-        int64_t lo = 0, hi = a.E;
-        while (lo < hi) {
-          const int64_t mid = (lo + hi) >> 1;
-          if (a.ex[mid] < x0) lo = mid + 1;
-          else hi = mid;
-        }
-        for (int64_t k = lo; k < a.E && !excluded && a.ex[k] == x0; ++k) {
-          bool all = true;
-          for (int c = 1; c < d && all; ++c) all = a.ex[(int64_t)c * a.E + k] == xr[c * EGO_ROWS];
-          excluded = all;
-        }
-      }
+      const bool excluded = ego_excluded(a.ex, a.E, d, xr, EGO_ROWS);
       if (a.mean_out) a.mean_out[row] = mean;
       if (a.var_out) a.var_out[row] = var;
       if (a.ei_out) a.ei_out[row] = excluded ? (double)NAN : ei;

@@ -443,6 +443,31 @@ struct EgoScan {
 hipError_t launch_ego_scan(const EgoScan& a, int max_blocks, const int* status, double* out,
                            hipStream_t s);
 
+// ---------------------------------------------------------------- k_scan.hip
+// The cheap knot proposals' scan (sgp_fit_scan): predict_laplace's mean and variance of a sparse
+// fit with m <= SGP_EGO_TMAX knots at every resident row, and the row of the largest key.
+struct FitScan {
+  const double* X;
+  int64_t ldx, n;
+  int d, m;
+  int mode;                  // 0: SGP_SCAN_VAR, 1: SGP_SCAN_ERROR (include/sgp.h)
+  double coef, sig2, c0;     // k = sig2 exp(coef sum_c ((x_c - u_c) rl_c)^2); c0 = sigma^2 + tau^2
+  const double* rl;          // d scales: 1 / l_c ("ard"), or ones ("sqexp": l sits in coef)
+  const double* mu;          // the rows' prior mean
+  const double* f;           // the rows' f (SGP_SCAN_ERROR)
+  const double* xu;          // knots, column-major, ld SGP_EGO_TMAX, zero padded rows
+  const double* A;           // K22^-1 - K22^-1 u_var K22^-1, SGP_EGO_TMAX^2, row-major
+  const double* w;           // K22^-1 (u_mean - muu), SGP_EGO_TMAX values, zero padded
+  const double* ex;          // excluded rows, E x d column-major (ld E), sorted by coordinate 0
+  int64_t E;
+  double *key_out, *mean_out, *var_out;   // n values each, or nullptr
+  double* rec;               // 2 doubles per workgroup (max_blocks of them)
+};
+// status: the K22 chain's status word; out (3 doubles): the winner's key, its row (-1: every row
+// excluded) and *status, written by the one-block final reduction
+hipError_t launch_fit_scan(const FitScan& a, int max_blocks, const int* status, double* out,
+                           hipStream_t s);
+
 // ---------------------------------------------------------------- k_score.hip
 // Held-out scoring (sgp_nlp): nlp[i] = my_nlp's value for row i (sgp_quad.h) and, per tile of
 // 256 rows, four partials in part (nlp_part_doubles(n) doubles).

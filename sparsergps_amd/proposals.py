@@ -1,8 +1,12 @@
-"""EGO knot proposals: the reference's ``xu_opt = "oat"`` proposal functions
+"""Knot proposals: the reference's ``xu_opt = "oat"`` / ``"random"`` proposal functions
 
   knot_prop_ego_norm_vi   R/vi_functions.R:1584-2104              (VI, scorer = the ELBO)
   knot_prop_ego_norm      R/knot_proposal_functions.R:498-999     (FITC, obj_fun_norm)
   knot_prop_ego           R/knot_proposal_functions.R:46-495      (Laplace, newtrap_sparseGP)
+  knot_prop_random*       R/vi_functions.R:2108-2311; R/knot_proposal_functions.R:1001-1365
+  knot_prop_var / _error  R/knot_proposal_functions.R:4-42        (at the end of this module)
+
+The EGO proposals first.
 
 All three are the same loop (``_ego_core``): score TTmin random data rows as an added knot, fit a
 small meta-model GP to (candidate, objective) pairs, scan every data row outside the knots for
@@ -287,3 +291,140 @@ def knot_prop_ego(laplace_opt, opt=None, *, y=None, ctx=None, m=1.0, family="poi
         return lambda cand: ctx.lap_candidates(theta, cov_fun, xu, cand, o["delta"], m,
                                                o["tol_nr"], o["maxit_nr"])
     return _run(laplace_opt, OPT_EGO, opt, ctx, y, make, rng, init_rows, meta_fit, trace)
+
+
+# ------------------------------------------------------------------ the random proposals
+# knot_prop_random_norm_vi (R/vi_functions.R:2108-2311), knot_prop_random_norm and
+# knot_prop_random (R/knot_proposal_functions.R:1176-1365, 1001-1171): TTmax random data rows
+# outside the knots, each scored as an added knot; no meta-model, and no TTmin.
+# opt defaults: vi_functions.R:2132-2135; knot_proposal_functions.R:1200-1203, 1030-1033
+_OPT_RANDOM = {"optim_method": "adadelta", "decay": 0.95, "epsilon": 1e-6, "learn_rate": 1e-2,
+               "eta": 0.8, "maxit": 1000, "obj_tol": 1e-3, "grad_tol": 1e-1, "maxit_nr": 1000,
+               "delta": 1e-6, "tol_knot": 1e-1, "maxknot": 30, "TTmax": 40}
+OPT_RANDOM_NORM_VI = dict(_OPT_RANDOM)
+OPT_RANDOM_NORM = dict(_OPT_RANDOM)
+OPT_RANDOM = {**_OPT_RANDOM, "tol_nr": 1e-4}
+
+
+def random_proposal(xy, xu, scorer, last_obj, o, rng=None, init_rows=None, trace=None):
+    """The loop shared by the three random proposals.  scorer(cand) -> objective values of the
+    k x d candidate knots (NaN = the reference's try-error); last_obj: the fit's last objective
+    value.  All TTmax first draws are scored in one scorer call; a NaN is resampled as the
+    reference resamples it (a random row outside the knots plus N(0, 1e-6^2) noise).
+
+    The return value is the reference's, quirk included (vi_functions.R:2188, 2302-2309): the
+    value vector starts with m copies of last_obj and obj_fun_x = rbind(xu, pseudo_prop), so
+    which.max returns the best candidate only if it beats the current objective strictly --
+    otherwise index 1, the FIRST EXISTING KNOT xu[0].  ``trace`` (a list) receives
+    {"rows", "vals", "best"}."""
+    xy = np.asarray(xy, dtype=np.float64)
+    xy = xy.reshape(xy.shape[0], -1)
+    d = xy.shape[1]
+    xu = np.asarray(xu, dtype=np.float64).reshape(-1, d)
+    TTmax = int(o["TTmax"])
+    pool = rows_outside_knots(xy, xu)
+    if init_rows is None:
+        if rng is None:
+            raise ValueError("give rng (a numpy Generator) or init_rows")
+        if pool.size < TTmax:
+            raise ValueError(f"{pool.size} data rows outside the knots, TTmax = {TTmax}")
+        init_rows = rng.choice(pool, size=TTmax, replace=False)   # sample.int, l.2209
+    init_rows = np.asarray(init_rows, dtype=np.int64).reshape(-1)
+    if init_rows.size != TTmax:
+        raise ValueError(f"init_rows has {init_rows.size} rows, TTmax = {TTmax}")
+    prop = xy[init_rows].copy()
+    vals = np.asarray(scorer(prop), dtype=np.float64).reshape(-1).copy()
+    for i in np.flatnonzero(np.isnan(vals)):   # in order, as the reference's loop resamples
+        while math.isnan(vals[i]):             # l.2254-2297
+            if rng is None:
+                raise ValueError("the scorer failed on a candidate and no rng was given to resample")
+            prop[i] = xy[pool[rng.integers(pool.size)]] + rng.normal(0.0, 1e-6, size=d)
+            vals[i] = float(np.asarray(scorer(prop[i].reshape(1, d))).reshape(-1)[0])
+    all_vals = np.concatenate([np.full(xu.shape[0], float(last_obj)), vals])   # l.2188, 2300
+    all_x = np.vstack([xu, prop])                                              # l.2302
+    best = int(np.argmax(all_vals))                                            # which.max
+    if trace is not None:
+        trace.append({"rows": init_rows.copy(), "vals": vals.copy(), "best": best})
+    return all_x[best].reshape(1, d).copy()
+
+
+def _run_random(fit, master, opt, ctx, y, make_scorer, rng, init_rows, trace):
+    o = _merge_opt(master, opt)
+    xy, xu, cov_fun, theta = _fit_parts(fit)
+    ctx = _context(ctx, fit, xy, xu, y)
+    scorer = make_scorer(ctx, o, theta, cov_fun, xu)
+    last = np.asarray(fit["obj_fun"], dtype=np.float64).reshape(-1)[-1]
+    return random_proposal(xy, xu, scorer, last, o, rng, init_rows, trace)
+
+
+def knot_prop_random_norm_vi(norm_opt, opt=None, *, y=None, ctx=None, rng=None, init_rows=None,
+                             trace=None):
+    """knot_prop_random_norm_vi (R/vi_functions.R:2108-2311): the best of TTmax random data rows
+    as one more knot of a VI fit (scorer = the ELBO at [xu; candidate]); see random_proposal for
+    the return value.  norm_opt needs xu, cov_par, cov_fun, xy, mu and obj_fun."""
+    def make(ctx, o, theta, cov_fun, xu):
+        return lambda cand: ctx.vi_candidates(theta, cov_fun, xu, cand, o["delta"])
+    return _run_random(norm_opt, OPT_RANDOM_NORM_VI, opt, ctx, y, make, rng, init_rows, trace)
+
+
+def knot_prop_random_norm(norm_opt, opt=None, *, y=None, ctx=None, rng=None, init_rows=None,
+                          trace=None):
+    """knot_prop_random_norm (R/knot_proposal_functions.R:1176-1365): the same for a FITC fit
+    (scorer obj_fun_norm at [xu; candidate])."""
+    def make(ctx, o, theta, cov_fun, xu):
+        return lambda cand: ctx.fitc_candidates(theta, cov_fun, xu, cand, o["delta"])
+    return _run_random(norm_opt, OPT_RANDOM_NORM, opt, ctx, y, make, rng, init_rows, trace)
+
+
+def knot_prop_random(laplace_opt, opt=None, *, y=None, ctx=None, m=1.0, family="poisson",
+                     rng=None, init_rows=None, trace=None):
+    """knot_prop_random (R/knot_proposal_functions.R:1001-1171): the same for a Laplace fit
+    (scorer = the last objective value of newtrap_sparseGP at [xu; candidate] started from the
+    fit's fmax, with opt's tol_nr / maxit_nr)."""
+    def make(ctx, o, theta, cov_fun, xu):
+        ctx.lap_set_family(family)
+        ctx.lap_set_f(laplace_opt["fmax"])
+        return lambda cand: ctx.lap_candidates(theta, cov_fun, xu, cand, o["delta"], m,
+                                               o["tol_nr"], o["maxit_nr"])
+    return _run_random(laplace_opt, OPT_RANDOM, opt, ctx, y, make, rng, init_rows, trace)
+
+
+# ------------------------------------------------------------------ the variance / error proposals
+def _scan_proposal(fit, mode, ctx, y, exclude_knots, trace):
+    xy = np.asarray(fit["xy"], dtype=np.float64)
+    xy = xy.reshape(xy.shape[0], -1)
+    xu = np.asarray(fit["xu"], dtype=np.float64).reshape(-1, xy.shape[1])
+    if ctx is None:
+        if y is None:
+            raise ValueError("give y or a SparseGPContext over (xy, y, mu)")
+        from .vi import SparseGPContext
+        ctx = SparseGPContext(xy, y, fit["mu"], m_max=xu.shape[0])
+    # the reference's call passes neither family nor delta (knot_proposal_functions.R:10-17,
+    # 30-37): predict_laplace's defaults, family = "gaussian" and delta = 1e-6, apply to every fit
+    res = ctx.fit_scan(fit["cov_par"], fit["cov_fun"], xu, fit["u_mean"], fit["u_var"], fit["muu"],
+                       mode, "gaussian", f=fit["fmax"] if mode == "error" else None,
+                       excl=xu if exclude_knots else None, delta=1e-6)
+    if trace is not None:
+        trace.append(dict(res))
+    return xy[res["row"]].reshape(1, -1).copy()
+
+
+def knot_prop_var(laplace_opt, opt=None, *, y=None, ctx=None, exclude_knots=False, trace=None,
+                  **_):
+    """knot_prop_var (R/knot_proposal_functions.R:4-20): the data row of the largest predictive
+    variance of the fit, as a 1 x d matrix, from one pass over the context's resident rows
+    (SparseGPContext.fit_scan).  The fit needs xu, cov_par, cov_fun, xy, mu, muu, u_mean, u_var.
+
+    Reference bug, not reproduced: pred_var is an n-vector there and l.18 takes
+    diag() of it, which builds an n x n matrix (n^2 doubles) whose which.max index is out of range
+    for xy unless row 1 wins.  Here: the row of largest variance, what the code intends.
+    exclude_knots=True leaves out rows that are knots already (the reference does not)."""
+    return _scan_proposal(laplace_opt, "var", ctx, y, exclude_knots, trace)
+
+
+def knot_prop_error(laplace_opt, opt=None, *, y=None, ctx=None, exclude_knots=False, trace=None,
+                    **_):
+    """knot_prop_error (R/knot_proposal_functions.R:24-42): the data row of the largest
+    |exp(fmax) - exp(pred_mean)| (l.38, written so for every family), as a 1 x d matrix.  The
+    fit also needs fmax."""
+    return _scan_proposal(laplace_opt, "error", ctx, y, exclude_knots, trace)

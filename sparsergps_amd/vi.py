@@ -51,6 +51,7 @@ class SparseGPContext:
         y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
         mu = np.ascontiguousarray(np.broadcast_to(np.asarray(mu, dtype=np.float64), y.shape))
         self.n, self.d = X.shape
+        self._X, self._mu = X, mu   # host rows and mean: fit_scan's route past its limits
         self.m_max = int(m_max)
         self.device = _device() if device is None else int(device)
         h = C.c_void_p()
@@ -92,6 +93,7 @@ class SparseGPContext:
         y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
         mu = np.ascontiguousarray(np.broadcast_to(np.asarray(mu, dtype=np.float64), y.shape))
         _lib.check(self._lib.sgp_ctx_set_data(self.handle, _lib.dptr(y), _lib.dptr(mu)))
+        self._mu = mu
 
     def enable_timing(self, on=True):
         _lib.check(self._lib.sgp_ctx_enable_timing(self.handle, 1 if on else 0))
@@ -410,6 +412,81 @@ class SparseGPContext:
             C.byref(row), C.byref(ei), *(None if k not in vecs else _lib.dptr(vecs[k])
                                          for k in ("ei", "mean", "var"))))
         return {"row": int(row.value), "best_ei": float(ei.value), **vecs}
+
+    def fit_scan(self, cov_par, cov_fun, xu, u_mean, u_var, muu, mode, family, f=None, excl=None,
+                 delta=1e-6, want=()):
+        """knot_prop_var / knot_prop_error's pass over this context's rows (sgp_fit_scan;
+        R/knot_proposal_functions.R:4-42): predict_laplace(full_cov = FALSE) of the fit
+        (``xu``, ``u_mean``, ``u_var``, ``muu``, ``cov_par`` of kind ``cov_fun``) at every row
+        with the context's mean, and the row of the largest key.  ``mode``: "var" (key = the
+        predictive variance) or "error" (key = |exp(f) - exp(mean)|, ``f`` = n values or None
+        for the resident Laplace mode).  ``family`` "gaussian" takes the gaussian Sigma22.  Rows
+        equal to a row of ``excl`` are left out (None, the reference's behaviour: none are).
+        Returns {"row" (0-based), "key"} plus, for each name in ``want``, the n-vector: "key"
+        (NaN on excluded rows), "mean", "var".  More than 128 knots, or a multi-device context,
+        take ``predict_laplace`` at the rows and a host arg-max instead."""
+        if mode not in ("var", "error"):
+            raise ValueError(f"mode must be 'var' or 'error', not {mode!r}")
+        bad = set(want) - {"key", "mean", "var"}
+        if bad:
+            raise ValueError(f"want: unknown vector(s) {sorted(bad)}")
+        U, m = self._knots(xu)
+        Ex, E = None, 0
+        if excl is not None:
+            Ex = np.asfortranarray(np.asarray(excl, dtype=np.float64).reshape(-1, self.d))
+            E = Ex.shape[0]
+        if f is not None:
+            f = np.ascontiguousarray(np.asarray(f, dtype=np.float64).reshape(-1))
+            if f.size != self.n:
+                raise ValueError(f"f has {f.size} values for {self.n} rows")
+        if m > _lib.SGP_EGO_TMAX or self.devices is not None:
+            return self._fit_scan_predict(cov_par, cov_fun, U, u_mean, u_var, muu, mode, family,
+                                          f, Ex, delta, want)
+        lnames = [f"l{c + 1}" for c in range(self.d)] if cov_fun == "ard" else None
+        theta = np.ascontiguousarray(theta_vector(cov_par, cov_fun, self.d, lnames))
+        um = np.ascontiguousarray(np.asarray(u_mean, dtype=np.float64).reshape(-1))
+        mu_u = np.ascontiguousarray(np.broadcast_to(np.asarray(muu, dtype=np.float64), (m,)))
+        uv = np.asfortranarray(np.asarray(u_var, dtype=np.float64).reshape(m, m))
+        if um.size != m:
+            raise ValueError(f"u_mean has {um.size} values for {m} knots")
+        vecs = {k: np.zeros(self.n, dtype=np.float64) for k in ("key", "mean", "var") if k in want}
+        row, key = C.c_int64(-1), C.c_double(0.0)
+        _lib.check(self._lib.sgp_fit_scan(
+            self.handle, _lib.KERNELS[cov_fun], _lib.dptr(theta), float(delta),
+            1 if family == "gaussian" else 0, _lib.dptr(U), m, m, _lib.dptr(um), _lib.dptr(mu_u),
+            _lib.dptr(uv), m, _lib.SGP_SCAN_ERROR if mode == "error" else _lib.SGP_SCAN_VAR,
+            None if f is None else _lib.dptr(f), None if Ex is None else _lib.dptr(Ex), E,
+            max(E, 1), C.byref(row), C.byref(key),
+            *(None if k not in vecs else _lib.dptr(vecs[k]) for k in ("key", "mean", "var"))))
+        return {"row": int(row.value), "key": float(key.value), **vecs}
+
+    def _fit_scan_predict(self, cov_par, cov_fun, U, u_mean, u_var, muu, mode, family, f, Ex,
+                          delta, want):
+        # the route every fit took before sgp_fit_scan: K(xy, xu) materialised by sgp_predict,
+        # two n-vectors read back, keys and which.max on the host
+        from .predict import predict_laplace
+        if mode == "error" and f is None:
+            f = self.lap_get_f()
+        pr = predict_laplace(u_mean, u_var, U, self._X, cov_fun, cov_par, self._mu, muu,
+                             full_cov=False, family=family, delta=delta)
+        mean = np.asarray(pr["pred_mean"], dtype=np.float64).reshape(-1)
+        var = np.asarray(pr["pred_var"], dtype=np.float64).reshape(-1)
+        key = np.abs(np.exp(f) - np.exp(mean)) if mode == "error" else var.copy()
+        if Ex is not None and Ex.shape[0]:
+            hit = (self._X[:, None, :] == Ex[None, :, :]).all(axis=2).any(axis=1)
+            key[hit] = np.nan
+            if hit.all():
+                raise _lib.SGPError(_lib.SGP_EINVAL, "sgp_fit_scan: every row is excluded")
+            cmp_key = np.where(np.isnan(key), -np.inf, key)
+            ok = np.flatnonzero(~hit)
+            row = int(ok[np.argmax(cmp_key[ok])])
+        else:
+            row = int(np.argmax(np.where(np.isnan(key), -np.inf, key)))
+        out = {"row": row, "key": float(key[row])}
+        for k, v in (("key", key), ("mean", mean), ("var", var)):
+            if k in want:
+                out[k] = v
+        return out
 
     def lap_nr(self, theta, cov_fun, xu, delta=1e-6, expo=1.0, tol=1e-5, maxit=1000):
         """newtrap_sparseGP alone from the resident f: (last objective value, NR iterations);
