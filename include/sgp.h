@@ -367,6 +367,67 @@ int sgp_predict_nlp(int device, int kernel, const double* theta, double delta, i
                     double* pred_var, int family, const double* y_pred, double par,
                     const double* expo, double* nlp, double* stats /* 4 */);
 
+/* Joint predictive scoring and draws from a Gaussian process: the branches of
+ * the reference that use a full covariance -- my_nlp(mv = TRUE), my_nlp(family = "bernoulli",
+ * mc = TRUE), my_kl(mv = TRUE) (R/evaluation_functions.R:21-26, 53-80, 120-133, 153-164) -- and the
+ * mvtnorm::rmvnorm draws its vignettes and exec/simulated_examples.R:15 begin with.  Device-level
+ * calls with host buffers, like sgp_nlp; covariances are n x n column-major, symmetric, and only
+ * their lower triangle is read.  They are factored A = L L^T on the device (right-looking
+ * Cholesky in 64-wide steps); one that is not positive definite is SGP_ENOTPD, naming the matrix
+ * and, as R's chol(), the order of the first leading minor that is not.
+ *
+ * The normal stream.  R's stream (rnorm by inversion on Mersenne-Twister, rmvnorm through an
+ * eigen-decomposition) cannot be reproduced; the draws come from a counter-based stream that is
+ * part of this interface, so that a host can regenerate every one:
+ *   generator  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9,
+ *              0xBB67AE85), key = (seed low 32 bits, seed high 32 bits)
+ *   output     words w0..w3: a = ((w1 << 32) | w0) >> 12, b = ((w3 << 32) | w2) >> 12,
+ *              u1 = (a + 0.5) 2^-52, u2 = (b + 0.5) 2^-52 (exact in fp64, inside (0, 1)),
+ *              r = sqrt(-2 log u1); the pair r cos(2 pi u2), r sin(2 pi u2)
+ *   stream 0   joint draws: draw s (0-based, 64-bit), row j (0-based) has the counter
+ *              (s low, s high, j >> 1, 0) and takes the cosine value for even j, the sine value
+ *              for odd j
+ *   stream 1   per-row Monte Carlo: draw t of row i has the counter (q low, q high, i, 1) with
+ *              q = t >> 1 and takes the cosine value for even t, the sine value for odd t
+ * Draw s is f = mean + L z with z_j the stream-0 normal of (s, j).  No result depends on how the
+ * draws are chunked or on the grid, and a repeat gives the same bits.
+ *
+ * SGP_EINVAL before any device call for: a NULL pointer (expo may be NULL), n < 1, S < 1 (where
+ * draws are taken), a leading dimension below n (ldo below S), an unknown family, sgp_nlp's per-row
+ * checks of y, par and expo, a non-finite mean, and n above SGP_JOINT_NMAX. */
+#define SGP_JOINT_NMAX 16384
+/* S draws from N(mean, cov): out is S x n column-major (ld ldo >= S), one draw per row, as
+ * rmvnorm returns them.  cov is used as given: the caller adds any nugget. */
+int sgp_sample_mvn(int device, const double* mean, const double* cov, int64_t n, int64_t ldc,
+                   int64_t S, uint64_t seed, double* out, int64_t ldo);
+/* my_nlp(mv = TRUE): out = {nlp, mcsd, nlp_se}.
+ *   SGP_FAM_GAUSSIAN   -dmvnorm(y, pred_mean, pred_cov + tau^2 I, log = TRUE) (l.23-25), par = tau,
+ *                      tau^2 added as written (quirk Q23); mcsd = nlp_se = NaN, S and seed unused
+ *   SGP_FAM_BERNOULLI, SGP_FAM_POISSON
+ *                      the reference's Monte Carlo estimate over S joint draws f_s (l.66-80,
+ *                      120-133), in log space: ll_s = sum_i log p(y_i | f_si) with
+ *                      p = dbinom(y, 1, my_logistic(f)) or dpois(y, exp(f) m) (par = m, or expo =
+ *                      n per-row exposures), lmax = max ll, w = exp(ll - lmax);
+ *                      nlp = -(lmax + log mean(w)), mcsd = exp(lmax) sd(w) (R's n - 1 form: NaN
+ *                      at S = 1; may underflow to 0), nlp_se = sd(w) / (mean(w) sqrt(S)).
+ *                      The reference's poisson branch calls dpois(x, size = 1, prob = ...), an R
+ *                      error; the evident intent dpois(y, exp(f) m) is built (quirk Q28). */
+int sgp_joint_nlp(int device, int family, const double* y, const double* pred_mean,
+                  const double* pred_cov, int64_t n, int64_t ldc, double par, const double* expo,
+                  int64_t S, uint64_t seed, double* out /* 3 */);
+/* my_kl(mv = TRUE) as written (l.155-163):
+ *   kl = 1/2 (tr(sigma2^-1 sigma1) + (mean2 - mean1)^T sigma2^-1 (mean2 - mean1) - n
+ *             + sum log diag chol2 - sum log diag chol1)
+ * whose last two terms are half the log-determinant difference, so the value is not the KL
+ * divergence (quirk Q29; parity is with the code). */
+int sgp_joint_kl(int device, const double* mean1, const double* mean2, const double* sigma1,
+                 int64_t ld1, const double* sigma2, int64_t ld2, int64_t n, double* kl);
+/* my_nlp(family = "bernoulli", mc = TRUE) (l.53-65): row i draws S values
+ * f = pred_mean_i + sqrt(pred_var_i) z from stream 1, ll = dbinom(y_i, 1, my_logistic(f));
+ * nlp[i] = -log mean(ll), mcsd[i] = sd(ll) (n - 1 form), in linear space as the reference. */
+int sgp_mc_nlp(int device, const double* y, const double* pred_mean, const double* pred_var,
+               int64_t n, int64_t S, uint64_t seed, double* nlp, double* mcsd);
+
 /* Knot gradients (xu_opt = "simultaneous"; the knot branches of delbo_dcov_par
  * R/vi_functions.R:425-593, dlogp_dcov_par R/laplace_approx_gradient.R:973-1126 and
  * dlogq_dcov_par 341-543, with dsqexp_dx2 / dsqexp_dx2_ard

@@ -64,6 +64,34 @@ int sgp_diag_nlp(int device, int family, int max_blocks, const double* y,
                  const double* pred_mean, const double* pred_var, int64_t n, double par,
                  const double* expo, double* nlp, double* stats, double* kernel_ms);
 
+/* The Cholesky factor the joint entries (sgp.h) use: A = L L^T for the n x n column-major A (ld
+ * lda; its lower triangle is read), L column-major (ld ldl) with its strict upper triangle zero,
+ * *logdet = 2 sum log L_ii.  SGP_ENOTPD with R's chol() message and order. */
+int sgp_diag_chol(int device, const double* A, int64_t n, int64_t lda, double* L, int64_t ldl,
+                  double* logdet);
+
+/* The normal stream of sgp.h as the device generates it: out is S x n column-major (ld S),
+ * out[s + S j] = the normal of draw s, row j of stream 0 or 1. */
+int sgp_diag_normals(int device, uint64_t seed, int stream, int64_t S, int64_t n, double* out);
+
+/* The yardstick of the draws' products: the generic f64 matrix-core GEMM they run on, timed on one
+ * square n x n x n product (n a multiple of 64) by HIP events; *best_ms = the best of reps launches
+ * after a warm-up. */
+int sgp_diag_gemm64(int device, int64_t n, int reps, double* best_ms);
+
+/* sgp_sample_mvn and sgp_joint_nlp (sgp.h) with their chunking and grid exposed: chunk_draws =
+ * draws per chunk (0 = the product's: the two n_p x S_c work matrices under 512 MB), max_blocks =
+ * the cap on the fill and scoring kernels' workgroups (0 = the product's).  The result must not
+ * depend on either.  stage_ms (or NULL): 4 doubles, the time by HIP events of the factor, the Z
+ * fills, the products and the scoring (with the final pass), each summed over the chunks. */
+int sgp_diag_sample_mvn(int device, int chunk_draws, int max_blocks, const double* mean,
+                        const double* cov, int64_t n, int64_t ldc, int64_t S, uint64_t seed,
+                        double* out, int64_t ldo, double* stage_ms);
+int sgp_diag_joint_nlp(int device, int family, int chunk_draws, int max_blocks, const double* y,
+                       const double* pred_mean, const double* pred_cov, int64_t n, int64_t ldc,
+                       double par, const double* expo, int64_t S, uint64_t seed, double* out,
+                       double* stage_ms);
+
 #ifdef __cplusplus
 }
 #endif

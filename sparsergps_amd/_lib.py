@@ -117,6 +117,26 @@ PROTOTYPES = {
                                   c_double_p, C.c_int64, c_double_p, C.c_int64, C.c_int64, C.c_int,
                                   c_double_p, c_double_p, c_double_p, C.c_int, c_double_p,
                                   C.c_double, c_double_p, c_double_p, c_double_p]),
+    "sgp_sample_mvn": (C.c_int, [C.c_int, c_double_p, c_double_p, C.c_int64, C.c_int64, C.c_int64,
+                                 C.c_uint64, c_double_p, C.c_int64]),
+    "sgp_joint_nlp": (C.c_int, [C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, C.c_int64,
+                                C.c_int64, C.c_double, c_double_p, C.c_int64, C.c_uint64,
+                                c_double_p]),
+    "sgp_joint_kl": (C.c_int, [C.c_int, c_double_p, c_double_p, c_double_p, C.c_int64, c_double_p,
+                               C.c_int64, C.c_int64, c_double_p]),
+    "sgp_mc_nlp": (C.c_int, [C.c_int, c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int64,
+                             C.c_uint64, c_double_p, c_double_p]),
+    "sgp_diag_chol": (C.c_int, [C.c_int, c_double_p, C.c_int64, C.c_int64, c_double_p, C.c_int64,
+                                c_double_p]),
+    "sgp_diag_normals": (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.c_int64, C.c_int64,
+                                   c_double_p]),
+    "sgp_diag_gemm64": (C.c_int, [C.c_int, C.c_int64, C.c_int, c_double_p]),
+    "sgp_diag_sample_mvn": (C.c_int, [C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, C.c_int64,
+                                      C.c_int64, C.c_int64, C.c_uint64, c_double_p, C.c_int64,
+                                      c_double_p]),
+    "sgp_diag_joint_nlp": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p,
+                                     c_double_p, C.c_int64, C.c_int64, C.c_double, c_double_p,
+                                     C.c_int64, C.c_uint64, c_double_p, c_double_p]),
     "sgp_ctx_enable_knot_grad": (C.c_int, [C.c_void_p, C.c_int]),
     "sgp_knot_red_extra": (C.c_int64, [C.c_int, C.c_int64]),
     "sgp_knot_gradient": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),

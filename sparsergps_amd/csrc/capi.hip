@@ -24,6 +24,7 @@
 #include "../../include/sgp.h"
 #include "../../include/sgp_diag.h"
 #include "sgp_internal.h"
+#include "sgp_quad.h"
 
 #ifdef SGP_HOST_PROBE
 // entry, before the readback's synchronisation, after it, exit of the last sgp_eval_vi
@@ -3636,6 +3637,465 @@ int sgp_predict_nlp(int device, int kernel, const double* theta, double delta, i
   const PredScore sc{family, y_pred, par, expo, nlp, stats};
   return predict_run(device, kernel, theta, delta, method, gaussian, U, m, ldu, u_mean, muu, u_var,
                      ldv, x_pred, np, ldxp, d, mu_pred, 0, pred_mean, pred_var, 0, &sc);
+}
+
+// ------------------------------------------------------- joint scoring and draws (k_joint.hip)
+namespace {
+// A covariance on the device and its Cholesky factor (dense_chol)
+struct CholWork {
+  DevBuf raw, A, L, Linv, logd;
+  IntBuf status;
+  int64_t n = 0, np = 0;
+  double logdet = 0.0;
+};
+
+// a stage's time by HIP events, added to *acc; off (no events, no waits) when acc == nullptr
+struct StageTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  double* acc = nullptr;
+  hipStream_t s = nullptr;
+  ~StageTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  hipError_t init(double* a, hipStream_t st) {
+    acc = a;
+    s = st;
+    if (!acc) return hipSuccess;
+    hipError_t e = hipEventCreate(&e0);
+    return e != hipSuccess ? e : hipEventCreate(&e1);
+  }
+  hipError_t begin() { return acc ? hipEventRecord(e0, s) : hipSuccess; }
+  hipError_t end(int stage) {
+    if (!acc) return hipSuccess;
+    hipError_t e = hipEventRecord(e1, s);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    acc[stage] += (double)ms;
+    return e;
+  }
+};
+
+bool all_finite(const double* v, int64_t n) {
+  for (int64_t i = 0; i < n; ++i)
+    if (!is_finite(v[i])) return false;
+  return true;
+}
+
+// cov (n x n column-major, ld ldc, lower triangle read) + diag_add I -> w.L, w.Linv, w.logdet.
+// SGP_ENOTPD names `name` and the order.  The upload and the Schur-complement copy are freed.
+int chol_factor(CholWork& w, const char* who, const char* name, const double* cov, int64_t n,
+                int64_t ldc, double diag_add, hipStream_t s, StageTimer* tm) {
+  const int64_t np = round_up(n, SGP_DB), nb = np / SGP_DB;
+  w.n = n;
+  w.np = np;
+  int st = dalloc(&w.raw.p, n * n);
+  st = st ? st : dalloc(&w.A.p, np * np);
+  st = st ? st : dalloc(&w.L.p, np * np);
+  st = st ? st : dalloc(&w.Linv.p, np * SGP_DB);
+  st = st ? st : dalloc(&w.logd.p, nb);
+  st = st ? st : dalloc(&w.status.p, 4);
+  if (st) return st;
+  HIPCHK(hipMemcpy2DAsync(w.raw.p, sizeof(double) * n, cov, sizeof(double) * ldc,
+                          sizeof(double) * n, (size_t)n, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(w.status.p, 0, sizeof(int) * 4, s));
+  HIPCHK(launch_chol_prep(w.raw.p, n, n, diag_add, w.A.p, np, s));
+  if (tm) HIPCHK(tm->begin());
+  HIPCHK(dense_chol(w.A.p, np, w.L.p, w.Linv.p, w.logd.p, w.status.p, s));
+  if (tm) HIPCHK(tm->end(0));
+  int hs[4];
+  std::vector<double> ld((size_t)nb);
+  HIPCHK(hipMemcpyAsync(hs, w.status.p, sizeof(hs), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(ld.data(), w.logd.p, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  (void)hipFree(w.raw.p);
+  w.raw.p = nullptr;
+  (void)hipFree(w.A.p);
+  w.A.p = nullptr;
+  if (hs[0]) {
+    set_err("%s: chol(): the leading minor of order %d of %s is not positive definite", who, hs[0],
+            name);
+    return SGP_ENOTPD;
+  }
+  double a = 0.0;
+  for (int64_t k = 0; k < nb; ++k) a += ld[(size_t)k];
+  w.logdet = 2.0 * a;
+  return SGP_OK;
+}
+
+// |L^-1 v|^2 for a host n-vector v: the solve on an np x 64 right-hand side whose first column is v
+int chol_quad(const CholWork& w, const double* v, hipStream_t s, double* q) {
+  const int64_t np = w.np, cnt = np * SGP_DB;
+  DevBuf B, X, part, out;
+  int st = dalloc(&B.p, cnt);
+  st = st ? st : dalloc(&X.p, cnt);
+  st = st ? st : dalloc(&part.p, 256);
+  st = st ? st : dalloc(&out.p, 1);
+  if (st) return st;
+  std::vector<double> h((size_t)cnt, 0.0);
+  for (int64_t i = 0; i < w.n; ++i) h[(size_t)(i * SGP_DB)] = v[i];
+  HIPCHK(hipMemcpyAsync(B.p, h.data(), sizeof(double) * cnt, hipMemcpyHostToDevice, s));
+  HIPCHK(chol_solve_lower(w.L.p, w.Linv.p, np, B.p, SGP_DB, X.p, s));
+  HIPCHK(launch_dot(X.p, X.p, cnt, part.p, out.p, s));
+  HIPCHK(hipMemcpyAsync(q, out.p, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return SGP_OK;
+}
+
+// draws per chunk: the workspace Z and F (2 np S_c doubles) stays under 512 MB; the chunks are
+// of equal length (a multiple of 64), so that the last one's padding stays below 64 columns each
+int64_t joint_chunk(int64_t np, int64_t S, int chunk_draws) {
+  if (chunk_draws > 0) return chunk_draws < S ? chunk_draws : S;
+  int64_t cap = ((int64_t)512 << 20) / (16 * np) / 64 * 64;
+  if (cap < 64) cap = 64;
+  const int64_t nchunk = (S + cap - 1) / cap;
+  const int64_t sc = round_up((S + nchunk - 1) / nchunk, 64);
+  return sc < S ? sc : S;
+}
+
+int joint_common_args(const char* who, const double* mean, int64_t n, int64_t ldc) {
+  if (n > SGP_JOINT_NMAX) {
+    set_err("%s: n = %lld above the limit %d", who, (long long)n, SGP_JOINT_NMAX);
+    return SGP_EINVAL;
+  }
+  if (ldc < n) {
+    set_err("%s: leading dimension %lld below n = %lld", who, (long long)ldc, (long long)n);
+    return SGP_EINVAL;
+  }
+  if (!all_finite(mean, n)) {
+    set_err("%s: the mean is not finite", who);
+    return SGP_EINVAL;
+  }
+  return SGP_OK;
+}
+
+// sgp_sample_mvn's body.  chunk_draws / max_blocks = 0: the product's; stage_ms (or NULL): 4
+// doubles {factor, Z fill, products, scoring} by HIP events
+int sample_run(int device, const double* mean, const double* cov, int64_t n, int64_t ldc,
+               int64_t S, uint64_t seed, double* out, int64_t ldo, int chunk_draws,
+               int max_blocks, double* stage_ms) {
+  const char* who = "sgp_sample_mvn";
+  if (!mean || !cov || !out || n < 1 || S < 1) {
+    set_err("%s: NULL argument, n < 1 or S < 1", who);
+    return SGP_EINVAL;
+  }
+  int st = joint_common_args(who, mean, n, ldc);
+  if (st) return st;
+  if (ldo < S) {
+    set_err("%s: leading dimension ldo = %lld below S = %lld", who, (long long)ldo, (long long)S);
+    return SGP_EINVAL;
+  }
+  if (chunk_draws < 0 || max_blocks < 0) {
+    set_err("%s: chunk_draws < 0 or max_blocks < 0", who);
+    return SGP_EINVAL;
+  }
+  HIPCHK(hipSetDevice(device));
+  if (max_blocks == 0 && (st = nlp_max_blocks(device, &max_blocks))) return st;
+  StreamGuard sg;
+  HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+  hipStream_t s = sg.s;
+  StageTimer tm;
+  if (stage_ms) stage_ms[0] = stage_ms[1] = stage_ms[2] = stage_ms[3] = 0.0;
+  HIPCHK(tm.init(stage_ms, s));
+  CholWork w;
+  if ((st = chol_factor(w, who, "cov", cov, n, ldc, 0.0, s, &tm))) return st;
+  const int64_t np = w.np, sc = joint_chunk(np, S, chunk_draws), ldz = round_up(sc, 64);
+  DevBuf dm, Z, F;
+  st = dalloc(&dm.p, n);
+  st = st ? st : dalloc(&Z.p, np * ldz);
+  st = st ? st : dalloc(&F.p, np * ldz);
+  if (st) return st;
+  HIPCHK(hipMemcpyAsync(dm.p, mean, sizeof(double) * n, hipMemcpyHostToDevice, s));
+  for (int64_t s0 = 0; s0 < S; s0 += sc) {
+    const int64_t cnt = S - s0 < sc ? S - s0 : sc;
+    HIPCHK(tm.begin());
+    HIPCHK(launch_joint_fill(seed, s0, cnt, ldz, n, np, dm.p, Z.p, F.p, max_blocks, s));
+    HIPCHK(tm.end(1));
+    HIPCHK(tm.begin());
+    HIPCHK(launch_joint_product(w.L.p, np, Z.p, F.p, ldz, s));
+    HIPCHK(tm.end(2));
+    // row i of F holds draws s0 .. s0 + cnt - 1 of f_i: column i of out, rows s0 ..
+    HIPCHK(hipMemcpy2DAsync(out + s0, sizeof(double) * ldo, F.p, sizeof(double) * ldz,
+                            sizeof(double) * cnt, (size_t)n, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return SGP_OK;
+}
+
+// sgp_joint_nlp's body (chunk_draws, max_blocks, stage_ms as sample_run)
+int joint_run(int device, int family, const double* y, const double* pred_mean,
+              const double* pred_cov, int64_t n, int64_t ldc, double par, const double* expo,
+              int64_t S, uint64_t seed, double* out, int chunk_draws, int max_blocks,
+              double* stage_ms) {
+  const char* who = "sgp_joint_nlp";
+  if (!pred_mean || !pred_cov) {
+    set_err("%s: NULL argument or n < 1", who);
+    return SGP_EINVAL;
+  }
+  int st = nlp_check_args(who, family, y, n, par, expo, out, out);
+  if (st) return st;
+  if ((st = joint_common_args(who, pred_mean, n, ldc))) return st;
+  if (family != SGP_FAM_GAUSSIAN && S < 1) {
+    set_err("%s: S = %lld < 1", who, (long long)S);
+    return SGP_EINVAL;
+  }
+  if (chunk_draws < 0 || max_blocks < 0) {
+    set_err("%s: chunk_draws < 0 or max_blocks < 0", who);
+    return SGP_EINVAL;
+  }
+  HIPCHK(hipSetDevice(device));
+  if (max_blocks == 0 && (st = nlp_max_blocks(device, &max_blocks))) return st;
+  StreamGuard sg;
+  HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+  hipStream_t s = sg.s;
+  StageTimer tm;
+  if (stage_ms) stage_ms[0] = stage_ms[1] = stage_ms[2] = stage_ms[3] = 0.0;
+  HIPCHK(tm.init(stage_ms, s));
+  CholWork w;
+  if (family == SGP_FAM_GAUSSIAN) {
+    // -dmvnorm(y, pred_mean, pred_cov + tau^2 I, log = TRUE) as written (quirk Q23)
+    if ((st = chol_factor(w, who, "pred_cov + tau^2 I", pred_cov, n, ldc, par * par, s, &tm)))
+      return st;
+    std::vector<double> r((size_t)n);
+    for (int64_t i = 0; i < n; ++i) r[(size_t)i] = y[i] - pred_mean[i];
+    double q = 0.0;
+    if ((st = chol_quad(w, r.data(), s, &q))) return st;
+    out[0] = 0.5 * ((double)n * 1.8378770664093454836 + w.logdet + q);   // log(2 pi)
+    out[1] = out[2] = nan("");
+    return SGP_OK;
+  }
+  if ((st = chol_factor(w, who, "pred_cov", pred_cov, n, ldc, 0.0, s, &tm))) return st;
+  const int64_t np = w.np, sc = joint_chunk(np, S, chunk_draws), ldz = round_up(sc, 64);
+  const bool pois = family == SGP_FAM_POISSON;
+  DevBuf dy, dm, da, Z, F, ll, dst;
+  st = dalloc(&dy.p, n);
+  st = st ? st : dalloc(&dm.p, n);
+  st = st ? st : dalloc(&Z.p, np * ldz);
+  st = st ? st : dalloc(&F.p, np * ldz);
+  st = st ? st : dalloc(&ll.p, S);
+  st = st ? st : dalloc(&dst.p, 3);
+  if (!st && pois) st = dalloc(&da.p, 3 * n);
+  if (st) return st;
+  HIPCHK(hipMemcpyAsync(dy.p, y, sizeof(double) * n, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dm.p, pred_mean, sizeof(double) * n, hipMemcpyHostToDevice, s));
+  std::vector<double> aux;
+  if (pois) {
+    // dpois(y, exp(f) m): the per-row constants log m_i, m_i, log(y_i!)
+    aux.resize((size_t)(3 * n));
+    for (int64_t i = 0; i < n; ++i) {
+      const double m = expo ? expo[i] : par;
+      aux[(size_t)i] = log(m);
+      aux[(size_t)(n + i)] = m;
+      aux[(size_t)(2 * n + i)] = quad_lfact(y[i]);
+    }
+    HIPCHK(hipMemcpyAsync(da.p, aux.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, s));
+  }
+  for (int64_t s0 = 0; s0 < S; s0 += sc) {
+    const int64_t cnt = S - s0 < sc ? S - s0 : sc;
+    HIPCHK(tm.begin());
+    HIPCHK(launch_joint_fill(seed, s0, cnt, ldz, n, np, dm.p, Z.p, F.p, max_blocks, s));
+    HIPCHK(tm.end(1));
+    HIPCHK(tm.begin());
+    HIPCHK(launch_joint_product(w.L.p, np, Z.p, F.p, ldz, s));
+    HIPCHK(tm.end(2));
+    HIPCHK(tm.begin());
+    HIPCHK(launch_joint_score(family, dy.p, pois ? da.p : nullptr, n, F.p, ldz, cnt, ll.p + s0,
+                              max_blocks, s));
+    HIPCHK(tm.end(3));
+  }
+  HIPCHK(tm.begin());
+  HIPCHK(launch_joint_stats(ll.p, S, dst.p, s));
+  HIPCHK(tm.end(3));
+  double hs[3];
+  HIPCHK(hipMemcpyAsync(hs, dst.p, sizeof(hs), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const double lmax = hs[0], mean = hs[1], sd = hs[2];
+  out[0] = -(lmax + log(mean));
+  out[1] = exp(lmax) * sd;
+  out[2] = sd / (mean * sqrt((double)S));
+  return SGP_OK;
+}
+}  // namespace
+
+int sgp_sample_mvn(int device, const double* mean, const double* cov, int64_t n, int64_t ldc,
+                   int64_t S, uint64_t seed, double* out, int64_t ldo) {
+  return sample_run(device, mean, cov, n, ldc, S, seed, out, ldo, 0, 0, nullptr);
+}
+
+int sgp_diag_sample_mvn(int device, int chunk_draws, int max_blocks, const double* mean,
+                        const double* cov, int64_t n, int64_t ldc, int64_t S, uint64_t seed,
+                        double* out, int64_t ldo, double* stage_ms) {
+  return sample_run(device, mean, cov, n, ldc, S, seed, out, ldo, chunk_draws, max_blocks,
+                    stage_ms);
+}
+
+int sgp_joint_nlp(int device, int family, const double* y, const double* pred_mean,
+                  const double* pred_cov, int64_t n, int64_t ldc, double par, const double* expo,
+                  int64_t S, uint64_t seed, double* out) {
+  return joint_run(device, family, y, pred_mean, pred_cov, n, ldc, par, expo, S, seed, out, 0, 0,
+                   nullptr);
+}
+
+int sgp_diag_joint_nlp(int device, int family, int chunk_draws, int max_blocks, const double* y,
+                       const double* pred_mean, const double* pred_cov, int64_t n, int64_t ldc,
+                       double par, const double* expo, int64_t S, uint64_t seed, double* out,
+                       double* stage_ms) {
+  return joint_run(device, family, y, pred_mean, pred_cov, n, ldc, par, expo, S, seed, out,
+                   chunk_draws, max_blocks, stage_ms);
+}
+
+int sgp_joint_kl(int device, const double* mean1, const double* mean2, const double* sigma1,
+                 int64_t ld1, const double* sigma2, int64_t ld2, int64_t n, double* kl) {
+  const char* who = "sgp_joint_kl";
+  if (!mean1 || !mean2 || !sigma1 || !sigma2 || !kl || n < 1) {
+    set_err("%s: NULL argument or n < 1", who);
+    return SGP_EINVAL;
+  }
+  int st = joint_common_args(who, mean1, n, ld1);
+  if (!st) st = joint_common_args(who, mean2, n, ld2);
+  if (st) return st;
+  HIPCHK(hipSetDevice(device));
+  StreamGuard sg;
+  HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+  hipStream_t s = sg.s;
+  CholWork w1, w2;
+  if ((st = chol_factor(w1, who, "sigma1", sigma1, n, ld1, 0.0, s, nullptr))) return st;
+  if ((st = chol_factor(w2, who, "sigma2", sigma2, n, ld2, 0.0, s, nullptr))) return st;
+  // my_kl(mv = TRUE) as written (R/evaluation_functions.R:155-163):
+  //   tr(sigma2^-1 sigma1) = |L2^-1 L1|_F^2, the padded identity's np - n ones taken off
+  const int64_t np = w1.np;
+  DevBuf X, part, out;
+  st = dalloc(&X.p, np * np);
+  st = st ? st : dalloc(&part.p, 256);
+  st = st ? st : dalloc(&out.p, 1);
+  if (st) return st;
+  HIPCHK(chol_solve_lower(w2.L.p, w2.Linv.p, np, w1.L.p, np, X.p, s));   // L1 is overwritten
+  HIPCHK(launch_dot(X.p, X.p, np * np, part.p, out.p, s));
+  double tr = 0.0, q = 0.0;
+  HIPCHK(hipMemcpyAsync(&tr, out.p, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  tr -= (double)(np - n);
+  std::vector<double> dmean((size_t)n);
+  for (int64_t i = 0; i < n; ++i) dmean[(size_t)i] = mean2[i] - mean1[i];
+  if ((st = chol_quad(w2, dmean.data(), s, &q))) return st;
+  // sum(log(diag(chol2))) - sum(log(diag(chol1))): half the log-determinant difference
+  *kl = 0.5 * (tr + q - (double)n + 0.5 * w2.logdet - 0.5 * w1.logdet);
+  return SGP_OK;
+}
+
+int sgp_mc_nlp(int device, const double* y, const double* pred_mean, const double* pred_var,
+               int64_t n, int64_t S, uint64_t seed, double* nlp, double* mcsd) {
+  const char* who = "sgp_mc_nlp";
+  if (!pred_mean || !pred_var || !mcsd) {
+    set_err("%s: NULL argument or n < 1", who);
+    return SGP_EINVAL;
+  }
+  int st = nlp_check_args(who, SGP_FAM_BERNOULLI, y, n, 0.0, nullptr, nlp, mcsd);
+  if (st) return st;
+  if (S < 1) {
+    set_err("%s: S = %lld < 1", who, (long long)S);
+    return SGP_EINVAL;
+  }
+  if (!all_finite(pred_mean, n)) {
+    set_err("%s: the mean is not finite", who);
+    return SGP_EINVAL;
+  }
+  HIPCHK(hipSetDevice(device));
+  StreamGuard sg;
+  HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+  hipStream_t s = sg.s;
+  DevBuf dy, dm, dv, dn, ds;
+  st = dalloc(&dy.p, n);
+  st = st ? st : dalloc(&dm.p, n);
+  st = st ? st : dalloc(&dv.p, n);
+  st = st ? st : dalloc(&dn.p, n);
+  st = st ? st : dalloc(&ds.p, n);
+  if (st) return st;
+  const size_t nb = sizeof(double) * (size_t)n;
+  HIPCHK(hipMemcpyAsync(dy.p, y, nb, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dm.p, pred_mean, nb, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dv.p, pred_var, nb, hipMemcpyHostToDevice, s));
+  HIPCHK(launch_mc_rows(seed, dy.p, dm.p, dv.p, n, S, dn.p, ds.p, s));
+  HIPCHK(hipMemcpyAsync(nlp, dn.p, nb, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(mcsd, ds.p, nb, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return SGP_OK;
+}
+
+int sgp_diag_chol(int device, const double* A, int64_t n, int64_t lda, double* L, int64_t ldl,
+                  double* logdet) {
+  const char* who = "sgp_diag_chol";
+  if (!A || !L || !logdet || n < 1) {
+    set_err("%s: NULL argument or n < 1", who);
+    return SGP_EINVAL;
+  }
+  if (n > SGP_JOINT_NMAX || lda < n || ldl < n) {
+    set_err("%s: n = %lld above the limit %d or a leading dimension below n", who, (long long)n,
+            SGP_JOINT_NMAX);
+    return SGP_EINVAL;
+  }
+  HIPCHK(hipSetDevice(device));
+  StreamGuard sg;
+  HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+  CholWork w;
+  int st = chol_factor(w, who, "A", A, n, lda, 0.0, sg.s, nullptr);
+  if (st) return st;
+  const int64_t np = w.np;
+  std::vector<double> h((size_t)(np * np));
+  HIPCHK(hipMemcpyAsync(h.data(), w.L.p, sizeof(double) * np * np, hipMemcpyDeviceToHost, sg.s));
+  HIPCHK(hipStreamSynchronize(sg.s));
+  for (int64_t j = 0; j < n; ++j)
+    for (int64_t i = 0; i < n; ++i) L[i + j * ldl] = h[(size_t)(i * np + j)];
+  *logdet = w.logdet;
+  return SGP_OK;
+}
+
+int sgp_diag_gemm64(int device, int64_t n, int reps, double* best_ms) {
+  if (!best_ms || n < 64 || n % 64 || n > SGP_JOINT_NMAX || reps < 1) {
+    set_err("sgp_diag_gemm64: NULL argument, n not a multiple of 64 in [64, %d] or reps < 1",
+            SGP_JOINT_NMAX);
+    return SGP_EINVAL;
+  }
+  HIPCHK(hipSetDevice(device));
+  StreamGuard sg;
+  HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+  DevBuf A, B, Cm;
+  int st = dalloc(&A.p, n * n);
+  st = st ? st : dalloc(&B.p, n * n);
+  st = st ? st : dalloc(&Cm.p, n * n);
+  if (st) return st;
+  HIPCHK(launch_normals(1, 0, n, n, A.p, sg.s));
+  HIPCHK(launch_normals(2, 0, n, n, B.p, sg.s));
+  double ms[1] = {0.0}, best = 0.0;
+  StageTimer tm;
+  HIPCHK(tm.init(ms, sg.s));
+  for (int r = 0; r <= reps; ++r) {   // the first launch is a warm-up
+    ms[0] = 0.0;
+    HIPCHK(tm.begin());
+    HIPCHK(launch_gemm64(false, false, false, n, n, n, 1.0, A.p, n, B.p, n, 0.0, Cm.p, n, sg.s));
+    HIPCHK(tm.end(0));
+    if (r == 1 || (r > 1 && ms[0] < best)) best = ms[0];
+  }
+  *best_ms = best;
+  return SGP_OK;
+}
+
+int sgp_diag_normals(int device, uint64_t seed, int stream, int64_t S, int64_t n, double* out) {
+  if (!out || S < 1 || n < 1 || (stream != 0 && stream != 1)) {
+    set_err("sgp_diag_normals: NULL argument, S < 1, n < 1 or a stream other than 0 and 1");
+    return SGP_EINVAL;
+  }
+  HIPCHK(hipSetDevice(device));
+  StreamGuard sg;
+  HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+  DevBuf d;
+  int st = dalloc(&d.p, S * n);
+  if (st) return st;
+  HIPCHK(launch_normals(seed, stream, S, n, d.p, sg.s));
+  HIPCHK(hipMemcpyAsync(out, d.p, sizeof(double) * S * n, hipMemcpyDeviceToHost, sg.s));
+  HIPCHK(hipStreamSynchronize(sg.s));
+  return SGP_OK;
 }
 
 namespace {

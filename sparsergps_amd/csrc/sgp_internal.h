@@ -489,6 +489,44 @@ hipError_t launch_nlp_rows(int fam, const NlpArgs& a, int max_blocks, double* st
 hipError_t launch_pred_finish(const double* mu_pred, const double* yv, const double* q, double c0,
                               int64_t np, double* pm, double* pv, hipStream_t s);
 
+// ---------------------------------------------------------------- k_joint.hip
+// Joint scoring and draws (sgp_sample_mvn, sgp_joint_nlp, sgp_joint_kl, sgp_mc_nlp).  Matrices
+// are np x np row-major, np a multiple of 64.
+// dst = the full symmetric matrix of the lower triangle of the column-major src (n x n, ld lds),
+// diag_add added to its diagonal, padded with the identity
+hipError_t launch_chol_prep(const double* src, int64_t n, int64_t lds, double diag_add,
+                            double* dst, int64_t np, hipStream_t s);
+// A = L L^T from A's lower triangle (A is overwritten by the Schur complements; L != A; L's strict
+// upper triangle is zeroed).  Linv: np x 64, the np / 64 inverses of L's diagonal blocks;
+// logd[k] = sum log L_jj over block k, so log det A = 2 sum_k logd[k]; *status (zero at the call):
+// the 1-based order of the first leading minor that is not positive definite
+hipError_t dense_chol(double* A, int64_t np, double* L, double* Linv, double* logd, int* status,
+                      hipStream_t s);
+// X = L^-1 B for B, X: np x N row-major (ld N, a multiple of 64); B is overwritten
+hipError_t chol_solve_lower(const double* L, const double* Linv, int64_t np, double* B, int64_t N,
+                            double* X, hipStream_t s);
+// One chunk of draws s0 .. s0 + sc - 1: Z (np x ldz, ldz >= sc a multiple of 64) from stream 0 of
+// sgp_rng.h, zero past row n and column sc, and F (np x ldz) = mean in every column
+hipError_t launch_joint_fill(uint64_t seed, int64_t s0, int64_t sc, int64_t ldz, int64_t n,
+                             int64_t np, const double* mean, double* Z, double* F,
+                             int max_blocks, hipStream_t s);
+// F += L Z, by block-row panels of L with K cut at each panel's last non-zero column
+hipError_t launch_joint_product(const double* L, int64_t np, const double* Z, double* F,
+                                int64_t ldz, hipStream_t s);
+// ll[s] = sum_{i < n} log p(y_i | F_is) for s < sc.  fam: SGP_FAM_BERNOULLI, or SGP_FAM_POISSON
+// with aux = {log m_i, m_i, log(y_i!)} (3 n values)
+hipError_t launch_joint_score(int fam, const double* y, const double* aux, int64_t n,
+                              const double* F, int64_t ldf, int64_t sc, double* ll,
+                              int max_blocks, hipStream_t s);
+// out (3 doubles) = {lmax, mean(w), sd(w)}, w = exp(ll - lmax), over all S values in one block
+hipError_t launch_joint_stats(const double* ll, int64_t S, double* out, hipStream_t s);
+// my_nlp(family = "bernoulli", mc = TRUE) with stream 1 of sgp_rng.h: nlp, mcsd (n values each)
+hipError_t launch_mc_rows(uint64_t seed, const double* y, const double* pm, const double* pv,
+                          int64_t n, int64_t S, double* nlp, double* mcsd, hipStream_t s);
+// out[s + S j] = the normal of draw s, row j of stream 0 or 1
+hipError_t launch_normals(uint64_t seed, int stream, int64_t S, int64_t n, double* out,
+                          hipStream_t s);
+
 // knot gradients (k_mfma.hip / k_cov.hip)
 // out[j*d + c] (+)= sum over row tiles of knot_slab (deterministic two-level reduction);
 // part: 64 * mp * d doubles of work space
