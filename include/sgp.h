@@ -367,6 +367,69 @@ int sgp_predict_nlp(int device, int kernel, const double* theta, double delta, i
                     double* pred_var, int family, const double* y_pred, double par,
                     const double* expo, double* nlp, double* stats /* 4 */);
 
+/* A resident predictor: sgp_predict(full_cov = 0) split into the work that
+ * depends on the fit alone, done once by sgp_predictor_create, and the work per batch of
+ * prediction rows, done by the run entries on any number of batches of any size.  The same
+ * reference functions, by `method` (all four SGP_PRED_*): predict_vi (R/vi_functions.R:1222-1333),
+ * predict_laplace (R/laplace_approx_prediction.R:3-123), predict_gp_full
+ * (R/laplace_approx_prediction.R:281-405) and predict_laplace_full
+ * (R/laplace_approx_prediction.R:128-214), as dispatched by predict_gp
+ * (R/laplace_approx_prediction.R:408-542).  Every method is
+ *   pred_mean_i = mu_pred_i + k_i^T w,   pred_var_i = c0 + k_i^T T22 k_i,   k_i = k(x_pred_i, U)
+ * with w (m), T22 (m x m, symmetric) and c0 fixed by the fit.
+ *
+ * create: arguments, their meaning per method and the errors are sgp_predict's.  SGP_EINVAL
+ * before the first device call (sgp_diag_predictor_args, sgp_diag.h, is the same check) for: a
+ * kernel other than SGP_KERNEL_SQEXP / SGP_KERNEL_ARD (SGP_KERNEL_EXP: optimize_gp.R:263), d
+ * outside [1, 32], an unknown method, a NULL pointer (u_var may be NULL for SGP_PRED_FULL and
+ * SGP_PRED_LAPLACE_FULL), m < 1, ldu < m, ldv < m (sparse methods), a non-finite theta, delta,
+ * u_mean, muu, U or u_var entry, sigma <= 0, tau < 0, a length scale <= 0, a W > 0
+ * (SGP_PRED_LAPLACE_FULL), and SGP_PRED_VI with gaussian = 0 (the reference's message).  A
+ * Sigma22 that is not positive definite is SGP_ENOTPD with sgp_predict's text and leading-minor
+ * order.  create runs sgp_predict's m x m stage once on a stream the predictor owns and keeps U,
+ * w, T22 (also in the symmetric block form the batches use) and c0 on `device`; full_cov stays
+ * with sgp_predict.
+ *
+ * run: host buffers.  x_pred (np x d column-major, ld ldxp) is streamed in chunks of rows (a
+ * multiple of 128 whose m-wide K work space stays within a fixed byte budget); np is limited by
+ * host memory only.  The K12 builder's form is chosen once from the column range of the whole
+ * x_pred, so every chunk uses it.  A row's result has a fixed summation order: it does not
+ * depend on the chunking or the repeat (bit-identical).
+ *
+ * run_nlp: run, then sgp_nlp of the result against y_pred without the round trip.  pred_mean and
+ * pred_var are bit-identical to run's, nlp and stats to sgp_nlp's on those vectors.  The
+ * scoring kernel's final pass adds its 256-row partials in an order that spans all rows (thread
+ * t takes tiles t, t + 256, ...), so stats cannot be carried from chunk to chunk bit for bit:
+ * pred_mean and pred_var are assembled on the device (16 np bytes) and scored once there.
+ * Arguments and errors of the scoring part as sgp_nlp's.
+ *
+ * run_dev: x_pred, mu_pred, pred_mean, pred_var are device pointers on the predictor's device
+ * (x_pred column-major with ld ldxp); the work is queued on `stream` (a hipStream_t, NULL = the
+ * null stream) and the call does not wait for it.  box_lo / box_hi: d host values each bounding
+ * every coordinate of x_pred (a wrong box costs accuracy in K, never memory safety), or NULL for
+ * the builder's exact-difference form.  With the box equal to x_pred's column range the result
+ * is bit-identical to run's.
+ *
+ * A predictor serves one run at a time (its chunk work space is shared): calls from one host
+ * thread on one stream are ordered by that stream; a caller that changes streams, or mixes
+ * run_dev with the host entries, synchronises the earlier stream first.  destroy waits for the
+ * predictor's own stream; NULL is SGP_EINVAL for run and destroy. */
+typedef struct sgp_predictor sgp_predictor;
+int sgp_predictor_create(sgp_predictor** out, int device, int kernel, const double* theta,
+                         double delta, int method, int gaussian, const double* U, int64_t m,
+                         int64_t ldu, int d, const double* u_mean, const double* muu,
+                         const double* u_var, int64_t ldv);
+int sgp_predictor_destroy(sgp_predictor* p);
+int sgp_predictor_run(sgp_predictor* p, const double* x_pred, int64_t np, int64_t ldxp,
+                      const double* mu_pred, double* pred_mean, double* pred_var);
+int sgp_predictor_run_nlp(sgp_predictor* p, const double* x_pred, int64_t np, int64_t ldxp,
+                          const double* mu_pred, double* pred_mean, double* pred_var, int family,
+                          const double* y_pred, double par, const double* expo, double* nlp,
+                          double* stats /* 4 */);
+int sgp_predictor_run_dev(sgp_predictor* p, const double* x_pred, int64_t np, int64_t ldxp,
+                          const double* mu_pred, double* pred_mean, double* pred_var,
+                          const double* box_lo, const double* box_hi, void* stream);
+
 /* Joint predictive scoring and draws from a Gaussian process: the branches of
  * the reference that use a full covariance -- my_nlp(mv = TRUE), my_nlp(family = "bernoulli",
  * mc = TRUE), my_kl(mv = TRUE) (R/evaluation_functions.R:21-26, 53-80, 120-133, 153-164) -- and the

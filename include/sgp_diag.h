@@ -92,6 +92,38 @@ int sgp_diag_joint_nlp(int device, int family, int chunk_draws, int max_blocks, 
                        double par, const double* expo, int64_t S, uint64_t seed, double* out,
                        double* stage_ms);
 
+/* Host only (no device is touched): the argument checks sgp_predictor_create (sgp.h) runs before
+ * its first device call -- the very function it calls.  SGP_OK or SGP_EINVAL with
+ * sgp_last_error(). */
+int sgp_diag_predictor_args(int d, int kernel, const double* theta, double delta, int method,
+                            int gaussian, const double* U, int64_t m, int64_t ldu,
+                            const double* u_mean, const double* muu, const double* u_var,
+                            int64_t ldv);
+
+/* Host only: the chunk plan of a predictor run over np rows with m knots.  budget_bytes = the K
+ * work space's byte budget (0 = the product's).  *chunk_rows: the largest multiple of 128 rows
+ * whose chunk_rows x round_up(m, 128) doubles stay within the budget (never below 128, never
+ * more than round_up(np, 128)); *nchunks = ceil(np / chunk_rows); per 128-row tile with nb =
+ * round_up(m, 128) / 128 column blocks, *block_products_sym = nb (nb + 1) / 2 128^3 block
+ * products of the symmetric block form and *block_products_full = nb^2 of the full one. */
+int sgp_diag_predictor_plan(int64_t m, int d, int64_t np, int64_t budget_bytes,
+                            int64_t* chunk_rows, int64_t* nchunks, int64_t* block_products_sym,
+                            int64_t* block_products_full);
+
+/* sgp_predictor_run (sgp.h) with its chunking and route exposed.  chunk_rows: rows per chunk, a
+ * multiple of 128 (0 = the product's; the work space grows to it).  route: 0 the product's; 1 the
+ * tile route (K built into the work space, the symmetric block form: k_pred.hip); 2
+ * sgp_predict's arithmetic on the chunk (the mean's row pass over K, then the full nb^2
+ * quadratic form): the A/B yardstick and a second cross-check; 3 the register route (K formed in
+ * registers, no K work space; SGP_EINVAL above 128 knots).  Routes agree to rounding, each is
+ * bit-identical over chunk_rows and on repeat.  stage_ms (or NULL): 4 doubles, the time by HIP
+ * events of the uploads, the K build, the mean / variance stage and the downloads, each summed
+ * over the chunks (with stage_ms the call waits for every chunk). */
+struct sgp_predictor;
+int sgp_diag_predictor_run(struct sgp_predictor* p, int64_t chunk_rows, int route,
+                           const double* x_pred, int64_t np, int64_t ldxp, const double* mu_pred,
+                           double* pred_mean, double* pred_var, double* stage_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ from .full import (dlogp_dcov_par_full, dlogq_dcov_par_full, full_eval, full_lap
                    obj_fun_norm_full, obj_fun_pois_full, predict_gp_full, predict_laplace_full)
 from .optimize import optimize_gp
 from .predict import predict_gp, predict_laplace, predict_vi
+from .predictor import Predictor, predictor_gp
 from .laplace import (dlogq_dcov_par, laplace_eval, newtrap_sparseGP, obj_fun_bern,
                       obj_fun_pois)
 from .knot_selection import (oat_knot_selection, oat_knot_selection_norm,
@@ -33,7 +34,7 @@ __all__ = [
     "SparseGPContext", "vi_eval", "elbo_fun", "delbo_dcov_par", "param_names",
     "fitc_eval", "dlogp_dcov_par",
     "laplace_eval", "newtrap_sparseGP", "dlogq_dcov_par", "obj_fun_pois", "obj_fun_bern",
-    "predict_vi", "predict_laplace", "predict_gp",
+    "predict_vi", "predict_laplace", "predict_gp", "Predictor", "predictor_gp",
     "norm_grad_ascent_vi", "norm_grad_ascent", "laplace_grad_ascent",
     "full_eval", "obj_fun_norm_full", "dlogp_dcov_par_full", "norm_grad_ascent_full",
     "predict_gp_full",

@@ -117,6 +117,29 @@ PROTOTYPES = {
                                   c_double_p, C.c_int64, c_double_p, C.c_int64, C.c_int64, C.c_int,
                                   c_double_p, c_double_p, c_double_p, C.c_int, c_double_p,
                                   C.c_double, c_double_p, c_double_p, c_double_p]),
+    "sgp_predictor_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, c_double_p,
+                                       C.c_double, C.c_int, C.c_int, c_double_p, C.c_int64,
+                                       C.c_int64, C.c_int, c_double_p, c_double_p, c_double_p,
+                                       C.c_int64]),
+    "sgp_predictor_destroy": (C.c_int, [C.c_void_p]),
+    "sgp_predictor_run": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, c_double_p,
+                                    c_double_p, c_double_p]),
+    "sgp_predictor_run_nlp": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, c_double_p,
+                                        c_double_p, c_double_p, C.c_int, c_double_p, C.c_double,
+                                        c_double_p, c_double_p, c_double_p]),
+    # device pointers (x_pred, mu_pred, pred_mean, pred_var) and the stream as addresses
+    "sgp_predictor_run_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, c_double_p, c_double_p,
+                                        C.c_void_p]),
+    "sgp_diag_predictor_args": (C.c_int, [C.c_int, C.c_int, c_double_p, C.c_double, C.c_int,
+                                          C.c_int, c_double_p, C.c_int64, C.c_int64, c_double_p,
+                                          c_double_p, c_double_p, C.c_int64]),
+    "sgp_diag_predictor_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int64, C.c_int64,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sgp_diag_predictor_run": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, c_double_p, C.c_int64,
+                                         C.c_int64, c_double_p, c_double_p, c_double_p,
+                                         c_double_p]),
     "sgp_sample_mvn": (C.c_int, [C.c_int, c_double_p, c_double_p, C.c_int64, C.c_int64, C.c_int64,
                                  C.c_uint64, c_double_p, C.c_int64]),
     "sgp_joint_nlp": (C.c_int, [C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, C.c_int64,

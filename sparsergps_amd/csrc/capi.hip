@@ -4309,6 +4309,547 @@ int predict_run(int device, int kernel, const double* theta, double delta, int m
 }
 }  // namespace
 
+// ------------------------------------------------------------------------- resident predictor
+// sgp_predictor_* (include/sgp.h): sgp_predict's m x m stage once, at create,
+// and then any number of batches streamed through a fixed chunk work space.
+struct sgp_predictor {
+  int device = 0;
+  hipStream_t stream = nullptr;   // non-blocking, owned: create and the host-buffer runs
+  KernParams kp;                  // without the builder's centre and span (set per run)
+  int d = 0, method = 0;
+  int64_t m = 0, mp = 0;
+  double c0 = 0.0;
+  std::vector<double> hU;         // m x d column-major (ld m): the centre and span of a run
+  // resident: knots (mp x d, ld mp), w (mp), T22 and its symmetric block form A' (mp x mp), the
+  // register route's -S and scales (mp = 128 only), the chain's status
+  double *dU = nullptr, *w = nullptr, *T22 = nullptr, *Ap = nullptr, *negA = nullptr,
+         *rl = nullptr, *scan_rec = nullptr;
+  int* status = nullptr;
+  int max_blocks = 1;
+  int64_t chunk_rows = 0;         // the product's chunk (SGP_PRED_BUDGET)
+  // chunk work space for `cap` rows: X (ld cap), K (cap x mp), mu, mean, var, the two slabs
+  int64_t cap = 0;
+  double *Xc = nullptr, *K = nullptr, *mu = nullptr, *pm = nullptr, *pv = nullptr,
+         *qslab = nullptr, *yslab = nullptr;
+};
+
+namespace {
+// The K work space's byte budget: of 64, 128, 256 and 1024 MiB at C3's rows with m = 1024 the
+// largest had the shortest call (profiles/predictor/README.md: the tile kernel itself is a
+// little faster at 256 MiB, the per-chunk copies and launches cost more than that)
+constexpr int64_t SGP_PRED_BUDGET = (int64_t)1024 << 20;
+// knots up to which route 0 takes the register route (k_fit_scan's pass)
+constexpr int64_t SGP_PRED_M0 = 64;
+
+void pred_free_ws(sgp_predictor* p) {
+  for (double** q : {&p->Xc, &p->K, &p->mu, &p->pm, &p->pv, &p->qslab, &p->yslab}) {
+    if (*q) (void)hipFree(*q);
+    *q = nullptr;
+  }
+  p->cap = 0;
+}
+
+void pred_free(sgp_predictor* p) {
+  if (!p) return;
+  (void)hipSetDevice(p->device);
+  if (p->stream) (void)hipStreamSynchronize(p->stream);
+  pred_free_ws(p);
+  for (double** q : {&p->dU, &p->w, &p->T22, &p->Ap, &p->negA, &p->rl, &p->scan_rec})
+    if (*q) (void)hipFree(*q);
+  if (p->status) (void)hipFree(p->status);
+  if (p->stream) (void)hipStreamDestroy(p->stream);
+  delete p;
+}
+
+struct PredGuard {
+  sgp_predictor* p = nullptr;
+  ~PredGuard() { pred_free(p); }
+};
+
+// The chunk plan: the largest multiple of 128 rows whose K work space stays within the budget
+// (never below one tile), no more than np needs.
+void pred_plan(int64_t m, int64_t np, int64_t budget, int64_t* chunk_rows, int64_t* nchunks) {
+  const int64_t mp = round_up(m, SGP_TILE);
+  int64_t rows = budget / (mp * (int64_t)sizeof(double)) / SGP_TILE * SGP_TILE;
+  if (rows < SGP_TILE) rows = SGP_TILE;
+  const int64_t need = round_up(np, SGP_TILE);
+  if (rows > need) rows = need;
+  *chunk_rows = rows;
+  *nchunks = (np + rows - 1) / rows;
+}
+
+int pred_ensure(sgp_predictor* p, int64_t rows) {
+  if (rows <= p->cap) return SGP_OK;
+  HIPCHK(hipStreamSynchronize(p->stream));
+  pred_free_ws(p);
+  const int64_t nb = p->mp / SGP_TILE;
+  int st = dalloc(&p->Xc, rows * p->d);
+  st = st ? st : dalloc(&p->K, rows * p->mp);
+  st = st ? st : dalloc(&p->mu, rows);
+  st = st ? st : dalloc(&p->pm, rows);
+  st = st ? st : dalloc(&p->pv, rows);
+  st = st ? st : dalloc(&p->qslab, rows * nb);
+  st = st ? st : dalloc(&p->yslab, rows * (nb < 2 ? 2 : nb));
+  if (st) {
+    pred_free_ws(p);
+    return st;
+  }
+  // rows past a chunk's end are read by the builder (and written as K = 0): finite values
+  HIPCHK(hipMemsetAsync(p->Xc, 0, sizeof(double) * rows * p->d, p->stream));
+  HIPCHK(hipStreamSynchronize(p->stream));
+  p->cap = rows;
+  return SGP_OK;
+}
+
+// The argument checks of sgp_predictor_create (sgp_diag_predictor_args); no device call.
+int pred_check_args(int d, int kernel, const double* theta, double delta, int method,
+                    int gaussian, const double* U, int64_t m, int64_t ldu, const double* u_mean,
+                    const double* muu, const double* u_var, int64_t ldv) {
+  if (kernel == SGP_KERNEL_EXP) {   // as sgp_predict: no fit carries it (optimize_gp.R:263)
+    set_err("sgp_predictor supports 'sqexp' and 'ard' (optimize_gp.R:263 rejects others)");
+    return SGP_EINVAL;
+  }
+  if (kernel != SGP_KERNEL_SQEXP && kernel != SGP_KERNEL_ARD) {
+    set_err("invalid covariance function (kernel=%d)", kernel);
+    return SGP_EINVAL;
+  }
+  if (d < 1 || d > SGP_MAXD) {
+    set_err("input dimension d=%d outside [1, %d]", d, SGP_MAXD);
+    return SGP_EINVAL;
+  }
+  if (method != SGP_PRED_VI && method != SGP_PRED_LAPLACE && method != SGP_PRED_FULL &&
+      method != SGP_PRED_LAPLACE_FULL) {
+    set_err("invalid prediction method %d", method);
+    return SGP_EINVAL;
+  }
+  const bool lapfull = method == SGP_PRED_LAPLACE_FULL;
+  const bool full = method == SGP_PRED_FULL || lapfull;
+  if (!theta || !U || !u_mean || !muu || (!u_var && !full)) {
+    set_err("sgp_predictor: theta, U, u_mean, muu and (sparse methods) u_var must not be NULL");
+    return SGP_EINVAL;
+  }
+  if (m < 1) {
+    set_err("sgp_predictor: m=%lld < 1", (long long)m);
+    return SGP_EINVAL;
+  }
+  if (ldu < m) {
+    set_err("sgp_predictor: ldu=%lld < m=%lld", (long long)ldu, (long long)m);
+    return SGP_EINVAL;
+  }
+  if (!full && ldv < m) {
+    set_err("sgp_predictor: ldv=%lld < m=%lld", (long long)ldv, (long long)m);
+    return SGP_EINVAL;
+  }
+  const int L = num_ls(kernel, d);
+  for (int p = 0; p < L + 2; ++p)
+    if (!std::isfinite(theta[p])) {
+      set_err("sgp_predictor: theta[%d] is not finite", p);
+      return SGP_EINVAL;
+    }
+  if (!(theta[0] > 0.0) || !(theta[L + 1] >= 0.0)) {
+    set_err("sgp_predictor: needs sigma > 0 and tau >= 0 (sigma=%g, tau=%g)", theta[0],
+            theta[L + 1]);
+    return SGP_EINVAL;
+  }
+  for (int p = 0; p < L; ++p)
+    if (!(theta[1 + p] > 0.0)) {
+      set_err("sgp_predictor: needs l > 0 (length scale %d is %g)", p + 1, theta[1 + p]);
+      return SGP_EINVAL;
+    }
+  if (!std::isfinite(delta)) {   // its sign is left to the factorisation, as in sgp_predict
+    set_err("sgp_predictor: delta=%g is not finite", delta);
+    return SGP_EINVAL;
+  }
+  for (int64_t j = 0; j < m; ++j) {
+    if (!std::isfinite(u_mean[j])) {
+      set_err("sgp_predictor: u_mean[%lld] is not finite", (long long)j);
+      return SGP_EINVAL;
+    }
+    if (!std::isfinite(muu[j])) {
+      set_err("sgp_predictor: muu[%lld] is not finite", (long long)j);
+      return SGP_EINVAL;
+    }
+  }
+  for (int q = 0; q < d; ++q)
+    for (int64_t j = 0; j < m; ++j)
+      if (!std::isfinite(U[j + q * ldu])) {
+        set_err("sgp_predictor: U[%lld, %d] is not finite", (long long)j, q);
+        return SGP_EINVAL;
+      }
+  for (int64_t k = 0; !full && k < m; ++k)
+    for (int64_t j = 0; j < m; ++j)
+      if (!std::isfinite(u_var[j + k * ldv])) {
+        set_err("sgp_predictor: u_var[%lld, %lld] is not finite", (long long)j, (long long)k);
+        return SGP_EINVAL;
+      }
+  for (int64_t j = 0; lapfull && j < m; ++j)
+    if (!(muu[j] <= 0.0)) {   // W = d2 log p(y|f) / df2 enters as sqrt(-W)
+      set_err("SGP_PRED_LAPLACE_FULL: W[%lld] = %g is not <= 0", (long long)j, muu[j]);
+      return SGP_EINVAL;
+    }
+  if (method == SGP_PRED_VI && !gaussian) {
+    set_err("Error: VI not supported for non-gaussian data.");   // predict_gp, l.424-427
+    return SGP_EINVAL;
+  }
+  return SGP_OK;
+}
+
+// One batch.  dev: x_pred, mu_pred, pred_mean, pred_var are device pointers and the work runs on
+// `s`; else host pointers, staged chunk by chunk on the predictor's stream.  box_lo / box_hi (d
+// host values each, or NULL: host buffers -> the column range of x_pred, device buffers -> the
+// builder's exact-difference form).  chunk_rows = 0 and route = 0: the product's.  sc: score the
+// assembled vectors on the device (host buffers only).
+int pred_run(sgp_predictor* p, int64_t chunk_rows, int route, const double* x_pred, int64_t np,
+             int64_t ldxp, const double* mu_pred, double* pred_mean, double* pred_var, bool dev,
+             const double* box_lo, const double* box_hi, hipStream_t s, const PredScore* sc,
+             double* stage_ms) {
+  if (!p) {
+    set_err("sgp_predictor: the predictor is NULL");
+    return SGP_EINVAL;
+  }
+  if (!x_pred || np < 1 || ldxp < np || !mu_pred || !pred_mean || !pred_var) {
+    set_err("invalid sgp_predictor_run arguments");
+    return SGP_EINVAL;
+  }
+  if (chunk_rows < 0 || chunk_rows % SGP_TILE) {
+    set_err("sgp_predictor: chunk_rows=%lld is not a non-negative multiple of %d",
+            (long long)chunk_rows, SGP_TILE);
+    return SGP_EINVAL;
+  }
+  if (route < 0 || route > 3) {
+    set_err("sgp_predictor: route=%d outside [0, 3]", route);
+    return SGP_EINVAL;
+  }
+  if (route == 3 && p->m > SGP_EGO_TMAX) {
+    set_err("sgp_predictor: the register route takes at most %d knots (m=%lld)", SGP_EGO_TMAX,
+            (long long)p->m);
+    return SGP_EINVAL;
+  }
+  if (route == 0) route = p->m <= SGP_PRED_M0 ? 3 : 1;
+  const int d = p->d;
+  const int64_t m = p->m, mp = p->mp;
+  KernParams kp = p->kp;
+  if (!dev) {
+    std::vector<double> plo, phi;
+    col_range(x_pred, np, ldxp, d, &plo, &phi);
+    set_center(&kp, p->hU.data(), m, m, plo.data(), phi.data());
+  } else {
+    set_center(&kp, p->hU.data(), m, m, box_lo && box_hi ? box_lo : nullptr,
+               box_lo && box_hi ? box_hi : nullptr);
+    if (!(box_lo && box_hi)) kp.span2 = INFINITY;
+  }
+  HIPCHK(hipSetDevice(p->device));
+  int64_t rows_max = 0, nchunks = 0;
+  if (chunk_rows > 0) {
+    rows_max = std::min(chunk_rows, round_up(np, SGP_TILE));
+    nchunks = (np + rows_max - 1) / rows_max;
+  } else {
+    pred_plan(m, np, SGP_PRED_BUDGET, &rows_max, &nchunks);
+  }
+  int st = pred_ensure(p, rows_max);
+  if (st) return st;
+  const int64_t cap = p->cap;
+  // scoring: the np-vectors assembled on the device (k_nlp_final's partial order spans all tiles)
+  DevBuf dpm, dpv, dy, de, dn, part, dst;
+  int max_blocks = 0;
+  if (sc) {
+    if ((st = nlp_max_blocks(p->device, &max_blocks))) return st;
+    st = dalloc(&dpm.p, np);
+    st = st ? st : dalloc(&dpv.p, np);
+    st = st ? st : dalloc(&dy.p, np);
+    st = st ? st : dalloc(&dn.p, np);
+    st = st ? st : dalloc(&part.p, nlp_part_doubles(np));
+    st = st ? st : dalloc(&dst.p, 4);
+    if (!st && sc->expo) st = dalloc(&de.p, np);
+    if (st) return st;
+  }
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  struct EvGuard {
+    hipEvent_t* e;
+    ~EvGuard() { for (int k = 0; k < 5; ++k) if (e[k]) (void)hipEventDestroy(e[k]); }
+  } evg{ev};
+  if (stage_ms) {
+    for (int k = 0; k < 4; ++k) stage_ms[k] = 0.0;
+    for (int k = 0; k < 5; ++k) HIPCHK(hipEventCreate(&ev[k]));
+  }
+  for (int64_t r0 = 0; r0 < np; r0 += rows_max) {
+    const int64_t rows = std::min(rows_max, np - r0), n_pad = round_up(rows, SGP_TILE);
+    const size_t rb = sizeof(double) * (size_t)rows;
+    if (stage_ms) HIPCHK(hipEventRecord(ev[0], s));
+    HIPCHK(hipMemcpy2DAsync(p->Xc, sizeof(double) * cap, x_pred + r0, sizeof(double) * ldxp, rb,
+                            (size_t)d, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    const double* mu = mu_pred + r0;
+    double *pm = pred_mean + r0, *pv = pred_var + r0;
+    if (!dev) {
+      HIPCHK(hipMemcpyAsync(p->mu, mu_pred + r0, rb, hipMemcpyHostToDevice, s));
+      mu = p->mu;
+      pm = sc ? dpm.p + r0 : p->pm;
+      pv = sc ? dpv.p + r0 : p->pv;
+    }
+    if (stage_ms) HIPCHK(hipEventRecord(ev[1], s));
+    if (route != 3)
+      HIPCHK(launch_build_knm(kp, p->Xc, cap, rows, n_pad, p->dU, mp, m, mp, p->K, s));
+    if (stage_ms) HIPCHK(hipEventRecord(ev[2], s));
+    if (route == 1) {
+      HIPCHK(launch_pred_tiles(p->K, p->Ap, p->w, rows, n_pad, cap, mp, mu, p->c0, p->qslab,
+                               p->yslab, pm, pv, s));
+    } else if (route == 2) {   // sgp_predict's arithmetic on the chunk
+      double *yv = p->yslab, *q = p->yslab + cap;
+      HIPCHK(launch_gemv_rows(p->K, n_pad, mp, p->w, nullptr, yv, nullptr, s));
+      HIPCHK(launch_rowquad_knm(kp, p->K, p->T22, rows, n_pad, m, mp, nullptr, 0.0, nullptr,
+                                nullptr, nullptr, p->qslab, q, s));
+      HIPCHK(launch_pred_finish(mu, yv, q, p->c0, rows, pm, pv, s));
+    } else {   // k_fit_scan's pass over the chunk: K in registers, var = c0 - k^T (-S) k
+      FitScan a;
+      a.X = p->Xc;
+      a.ldx = cap;
+      a.n = rows;
+      a.d = d;
+      a.m = (int)m;
+      a.mode = SGP_SCAN_VAR;
+      a.coef = kp.coef;
+      a.sig2 = kp.sig2;
+      a.c0 = p->c0;
+      a.rl = p->rl;
+      a.mu = mu;
+      a.f = nullptr;
+      a.xu = p->dU;
+      a.A = p->negA;
+      a.w = p->w;
+      a.ex = nullptr;
+      a.E = 0;
+      a.key_out = nullptr;
+      a.mean_out = pm;
+      a.var_out = pv;
+      a.rec = p->scan_rec;
+      HIPCHK(launch_fit_scan(a, p->max_blocks, p->status, p->scan_rec + 2 * p->max_blocks, s));
+    }
+    if (stage_ms) HIPCHK(hipEventRecord(ev[3], s));
+    if (!dev && !sc) {
+      HIPCHK(hipMemcpyAsync(pred_mean + r0, p->pm, rb, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(pred_var + r0, p->pv, rb, hipMemcpyDeviceToHost, s));
+    }
+    if (stage_ms) {
+      HIPCHK(hipEventRecord(ev[4], s));
+      HIPCHK(hipStreamSynchronize(s));
+      for (int k = 0; k < 4; ++k) {
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+        stage_ms[k] += (double)ms;
+      }
+    }
+    // (the next chunk reuses the work space in stream order: no host wait between chunks)
+  }
+  if (sc) {
+    const size_t nb = sizeof(double) * (size_t)np;
+    HIPCHK(hipMemcpyAsync(dy.p, sc->y, nb, hipMemcpyHostToDevice, s));
+    if (sc->expo) HIPCHK(hipMemcpyAsync(de.p, sc->expo, nb, hipMemcpyHostToDevice, s));
+    NlpArgs a{dy.p, dpm.p, dpv.p, sc->expo ? de.p : nullptr, sc->par, np, dn.p, part.p};
+    HIPCHK(launch_nlp_rows(sc->family, a, max_blocks, dst.p, s));
+    HIPCHK(hipMemcpyAsync(pred_mean, dpm.p, nb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pred_var, dpv.p, nb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sc->nlp, dn.p, nb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sc->stats, dst.p, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (!dev) HIPCHK(hipStreamSynchronize(s));
+  return SGP_OK;
+}
+}  // namespace
+
+int sgp_diag_predictor_args(int d, int kernel, const double* theta, double delta, int method,
+                            int gaussian, const double* U, int64_t m, int64_t ldu,
+                            const double* u_mean, const double* muu, const double* u_var,
+                            int64_t ldv) {
+  return pred_check_args(d, kernel, theta, delta, method, gaussian, U, m, ldu, u_mean, muu, u_var,
+                         ldv);
+}
+
+int sgp_diag_predictor_plan(int64_t m, int d, int64_t np, int64_t budget_bytes,
+                            int64_t* chunk_rows, int64_t* nchunks, int64_t* block_products_sym,
+                            int64_t* block_products_full) {
+  if (m < 1 || d < 1 || d > SGP_MAXD || np < 1 || budget_bytes < 0 || !chunk_rows || !nchunks ||
+      !block_products_sym || !block_products_full) {
+    set_err("sgp_diag_predictor_plan: invalid arguments");
+    return SGP_EINVAL;
+  }
+  pred_plan(m, np, budget_bytes ? budget_bytes : SGP_PRED_BUDGET, chunk_rows, nchunks);
+  const int64_t nb = round_up(m, SGP_TILE) / SGP_TILE;
+  *block_products_sym = nb * (nb + 1) / 2;
+  *block_products_full = nb * nb;
+  return SGP_OK;
+}
+
+int sgp_predictor_create(sgp_predictor** out, int device, int kernel, const double* theta,
+                         double delta, int method, int gaussian, const double* U, int64_t m,
+                         int64_t ldu, int d, const double* u_mean, const double* muu,
+                         const double* u_var, int64_t ldv) {
+  if (!out) {
+    set_err("sgp_predictor_create: out is NULL");
+    return SGP_EINVAL;
+  }
+  *out = nullptr;
+  int st = pred_check_args(d, kernel, theta, delta, method, gaussian, U, m, ldu, u_mean, muu,
+                           u_var, ldv);
+  if (st) return st;
+  KernParams kp;
+  if ((st = make_params(kernel, d, theta, delta, &kp))) return st;
+  const bool lapfull = method == SGP_PRED_LAPLACE_FULL;
+  const bool full = method == SGP_PRED_FULL || lapfull;
+  HIPCHK(hipSetDevice(device));
+  PredGuard g;
+  sgp_predictor* p = g.p = new sgp_predictor;
+  p->device = device;
+  p->kp = kp;
+  p->d = d;
+  p->method = method;
+  p->m = m;
+  const int64_t mp = p->mp = round_up(m, SGP_TILE), mm = mp * mp;
+  // vi_functions.R:1321: tau^2 + sigma^2 + delta; laplace_approx_prediction.R:114: sigma^2 + tau^2
+  // predict_gp_full: diag(Sigma11) = sigma^2 + tau^2 + delta
+  p->c0 = (method == SGP_PRED_VI) ? (kp.tau2 + kp.sig2) + delta
+                                  : (full ? (kp.sig2 + kp.tau2) + delta : kp.sig2 + kp.tau2);
+  p->hU.assign((size_t)(m * d), 0.0);
+  for (int c = 0; c < d; ++c)
+    for (int64_t j = 0; j < m; ++j) p->hU[(size_t)(c * m + j)] = U[j + c * ldu];
+  int64_t nchunks = 0;
+  pred_plan(m, INT64_MAX / 2, SGP_PRED_BUDGET, &p->chunk_rows, &nchunks);
+  int cus = 0;
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  p->max_blocks = std::min(4096, std::max(1, 8 * cus));
+  HIPCHK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  hipStream_t s = p->stream;
+  // the m x m stage of sgp_predict (predict_run), its temporaries freed when create returns
+  DevBuf K22, Kinv, R, Pb, logd, V, T1, wv;
+  IntBuf gsync;
+  const bool reg = mp == SGP_EGO_TMAX;   // the register route's operands
+  st = dalloc(&p->dU, mp * d);
+  st = st ? st : dalloc(&p->w, mp);
+  st = st ? st : dalloc(&p->T22, mm);
+  st = st ? st : dalloc(&p->Ap, mm);
+  st = st ? st : dalloc(&p->status, 4);
+  if (!st && reg) {
+    st = dalloc(&p->negA, mm);
+    st = st ? st : dalloc(&p->rl, SGP_MAXD);
+    st = st ? st : dalloc(&p->scan_rec, 2 * p->max_blocks + 4);
+  }
+  st = st ? st : dalloc(&K22.p, mm);
+  st = st ? st : dalloc(&Kinv.p, mm);
+  st = st ? st : dalloc(&R.p, mm);
+  st = st ? st : dalloc(&Pb.p, mp * 64);
+  st = st ? st : dalloc(&logd.p, mp / SGP_DB);
+  st = st ? st : dalloc(&V.p, mm);
+  st = st ? st : dalloc(&T1.p, mm);
+  st = st ? st : dalloc(&wv.p, 2 * mp);
+  st = st ? st : dalloc(&gsync.p, SGP_GJ_SYNC_WORDS);
+  if (st) return st;
+  // (the host buffers outlive the copies: the stream is synchronised before they go)
+  std::vector<double> hU((size_t)(mp * d), 0.0), hd((size_t)mp, 0.0), hg((size_t)mp, 0.0),
+      hV((size_t)mm, 0.0), hrl((size_t)SGP_MAXD, 1.0);
+  for (int c = 0; c < d; ++c)
+    for (int64_t j = 0; j < m; ++j) hU[(size_t)(c * mp + j)] = U[j + c * ldu];
+  for (int64_t j = 0; j < m; ++j) {
+    hd[(size_t)j] = lapfull ? sqrt(-muu[j]) : u_mean[j] - muu[j];   // lapfull: sqrt(-W)
+    hg[(size_t)j] = u_mean[j];
+  }
+  if (!full)
+    for (int64_t i = 0; i < m; ++i)
+      for (int64_t j = 0; j < m; ++j) hV[(size_t)(i * mp + j)] = u_var[i + j * ldv];
+  if (kernel == SGP_KERNEL_ARD)
+    for (int q = 0; q < d; ++q) hrl[(size_t)q] = kp.rl[q];
+  const size_t mb = sizeof(double) * (size_t)mp;
+  HIPCHK(hipMemcpyAsync(p->dU, hU.data(), sizeof(double) * hU.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(wv.p + mp, hd.data(), mb, hipMemcpyHostToDevice, s));
+  if (lapfull) HIPCHK(hipMemcpyAsync(p->w, hg.data(), mb, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(V.p, hV.data(), sizeof(double) * mm, hipMemcpyHostToDevice, s));
+  if (reg)
+    HIPCHK(hipMemcpyAsync(p->rl, hrl.data(), sizeof(double) * SGP_MAXD, hipMemcpyHostToDevice, s));
+  // on the launch stream: the null stream's hipMemset is not ordered before a non-blocking
+  // stream's kernels (the chain's sync words must be zero when it starts)
+  HIPCHK(hipMemsetAsync(p->status, 0, sizeof(int) * 4, s));
+  HIPCHK(hipMemsetAsync(gsync.p, 0, sizeof(int) * SGP_GJ_SYNC_WORDS, s));
+  // Sigma22: the gaussian family subtracts tau^2 I again (vi_functions.R:1246-1260,
+  // laplace_approx_prediction.R:25-43) -> diagonal sigma^2 + delta; otherwise Kuu+(tau^2+delta)I
+  // (predict_gp_full, laplace_approx_prediction.R:281-405: Sigma22 = k(xy, xy) + (tau^2+delta) I)
+  const double diag_sub = (gaussian && !full) ? kp.tau2 : 0.0;
+  HIPCHK(launch_build_kmm(kp, p->dU, mp, m, mp, diag_sub, K22.p, s));
+  if (lapfull) {
+    // temp22 = -R, R = sW (I + sW Sigma sW)^-1 sW (laplace_approx_prediction.R:169, 188, 206);
+    // the mean's multiplier grad_log_py_ff is in w already (l.209)
+    HIPCHK(launch_flap_scale(true, K22.p, wv.p + mp, Kinv.p, mp, m, s));
+    HIPCHK(dense_spd_inverse(Kinv.p, mp, R.p, Pb.p, logd.p, p->status,
+                             reinterpret_cast<unsigned*>(gsync.p), s));
+    HIPCHK(launch_flap_scale(false, Kinv.p, wv.p + mp, Kinv.p, mp, m, s));
+    HIPCHK(dense_axpby(0.0, V.p, -1.0, Kinv.p, p->T22, mm, s));   // V holds zeros
+  } else {
+    HIPCHK(hipMemcpyAsync(Kinv.p, K22.p, sizeof(double) * mm, hipMemcpyDeviceToDevice, s));
+    HIPCHK(dense_spd_inverse(Kinv.p, mp, R.p, Pb.p, logd.p, p->status,
+                             reinterpret_cast<unsigned*>(gsync.p), s));
+    HIPCHK(dense_gemv(Kinv.p, mp, wv.p + mp, 1.0, p->w, s));        // Sigma22^-1 (u_mean - muu)
+    HIPCHK(launch_gemm64(false, false, false, mp, mp, mp, 1.0, Kinv.p, mp, V.p, mp, 0.0, T1.p, mp,
+                         s));
+    HIPCHK(launch_gemm64(false, false, false, mp, mp, mp, 1.0, T1.p, mp, Kinv.p, mp, 0.0, p->T22,
+                         mp, s));                                     // Sigma22^-1 u_var Sigma22^-1
+    HIPCHK(dense_axpby(1.0, p->T22, -1.0, Kinv.p, p->T22, mm, s));   // temp22
+  }
+  HIPCHK(launch_pred_sym(p->T22, mp, p->Ap, s));
+  if (reg) HIPCHK(dense_axpby(0.0, p->Ap, -1.0, p->Ap, p->negA, mm, s));   // one block: A' = S
+  int hst[4];
+  HIPCHK(hipMemcpyAsync(hst, p->status, sizeof(hst), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (hst[0]) {
+    set_err("%s is not positive definite (leading minor of order %d)",
+            lapfull ? "I + sqrt(-W) %*% Sigma %*% sqrt(-W)" : "Sigma22", hst[0]);
+    return SGP_ENOTPD;
+  }
+  g.p = nullptr;
+  *out = p;
+  return SGP_OK;
+}
+
+int sgp_predictor_destroy(sgp_predictor* p) {
+  if (!p) {
+    set_err("sgp_predictor_destroy: the predictor is NULL");
+    return SGP_EINVAL;
+  }
+  pred_free(p);
+  return SGP_OK;
+}
+
+int sgp_predictor_run(sgp_predictor* p, const double* x_pred, int64_t np, int64_t ldxp,
+                      const double* mu_pred, double* pred_mean, double* pred_var) {
+  return pred_run(p, 0, 0, x_pred, np, ldxp, mu_pred, pred_mean, pred_var, false, nullptr,
+                  nullptr, p ? p->stream : nullptr, nullptr, nullptr);
+}
+
+int sgp_predictor_run_nlp(sgp_predictor* p, const double* x_pred, int64_t np, int64_t ldxp,
+                          const double* mu_pred, double* pred_mean, double* pred_var, int family,
+                          const double* y_pred, double par, const double* expo, double* nlp,
+                          double* stats) {
+  if (!p) {
+    set_err("sgp_predictor_run_nlp: the predictor is NULL");
+    return SGP_EINVAL;
+  }
+  int st = nlp_check_args("sgp_predictor_run_nlp", family, y_pred, np, par, expo, nlp, stats);
+  if (st) return st;
+  PredScore sc{family, y_pred, par, expo, nlp, stats};
+  return pred_run(p, 0, 0, x_pred, np, ldxp, mu_pred, pred_mean, pred_var, false, nullptr,
+                  nullptr, p->stream, &sc, nullptr);
+}
+
+int sgp_predictor_run_dev(sgp_predictor* p, const double* x_pred, int64_t np, int64_t ldxp,
+                          const double* mu_pred, double* pred_mean, double* pred_var,
+                          const double* box_lo, const double* box_hi, void* stream) {
+  return pred_run(p, 0, 0, x_pred, np, ldxp, mu_pred, pred_mean, pred_var, true, box_lo, box_hi,
+                  static_cast<hipStream_t>(stream), nullptr, nullptr);
+}
+
+int sgp_diag_predictor_run(sgp_predictor* p, int64_t chunk_rows, int route, const double* x_pred,
+                           int64_t np, int64_t ldxp, const double* mu_pred, double* pred_mean,
+                           double* pred_var, double* stage_ms) {
+  return pred_run(p, chunk_rows, route, x_pred, np, ldxp, mu_pred, pred_mean, pred_var, false,
+                  nullptr, nullptr, p ? p->stream : nullptr, nullptr, stage_ms);
+}
+
 
 // ------------------------------------------------------------------------- OAT candidates
 // ELBO of the knot sets [U; x*_t] for T candidate knots at fixed theta, as the meta-model

@@ -489,6 +489,19 @@ hipError_t launch_nlp_rows(int fam, const NlpArgs& a, int max_blocks, double* st
 hipError_t launch_pred_finish(const double* mu_pred, const double* yv, const double* q, double c0,
                               int64_t np, double* pm, double* pv, hipStream_t s);
 
+// ---------------------------------------------------------------- k_pred.hip
+// The resident predictor's tile route (sgp_predictor_*).  Ap (mp x mp row-major) from T22: with
+// S = (T22 + T22^T) / 2 and 128-blocks [kb, cb], Ap = 2 S above the block diagonal, S on it, 0
+// below, so that k^T T22 k = sum_cb k_cb . (sum_{kb <= cb} Ap[kb, cb]^T k_kb).
+hipError_t launch_pred_sym(const double* T22, int64_t mp, double* Ap, hipStream_t s);
+// pm_i = mu_i + K_i w, pv_i = c0 + K_i T22 K_i^T for i < n from K (n_pad x mp row-major, n_pad a
+// multiple of 128, zero in rows >= n and columns >= m).  qslab, yslab: (mp / 128) x ld doubles
+// each (ld >= n_pad); mu, pm, pv: n values.  Fixed summation order per row.
+hipError_t launch_pred_tiles(const double* K, const double* Ap, const double* w, int64_t n,
+                             int64_t n_pad, int64_t ld, int64_t mp, const double* mu, double c0,
+                             double* qslab, double* yslab, double* pm, double* pv,
+                             hipStream_t s);
+
 // ---------------------------------------------------------------- k_joint.hip
 // Joint scoring and draws (sgp_sample_mvn, sgp_joint_nlp, sgp_joint_kl, sgp_mc_nlp).  Matrices
 // are np x np row-major, np a multiple of 64.
