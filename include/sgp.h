@@ -430,6 +430,57 @@ int sgp_predictor_run_dev(sgp_predictor* p, const double* x_pred, int64_t np, in
                           const double* mu_pred, double* pred_mean, double* pred_var,
                           const double* box_lo, const double* box_hi, void* stream);
 
+/* A batch of small-knot VI problems: B independent Titsias-VI problems, each
+ * with its own rows, theta and at most SGP_BATCH_MMAX knots, evaluated together in four kernel
+ * launches (the folds of a cross-validation, repeated splits, the starts of a multi-start search).
+ * Per problem the semantics are exactly sgp_eval_vi's: K22 = Kuu + delta I, Z = tau^2 + delta,
+ * elbo_fun (R/vi_functions.R:64-121), trace_term_fun (R/vi_functions.R:14-27) and delbo_dcov_par
+ * (R/vi_functions.R:126-419) with the gradient in log theta in sgp_num_params order, knots fixed,
+ * the tau coincidence rule (quirk Q5) for rows that equal a knot exactly, and SGP_FLAG_R_DET /
+ * SGP_FLAG_OBJ_ONLY with their sgp_eval_vi meaning (SGP_FLAG_OBJ_ONLY skips the second row pass).
+ *
+ * create: X (nrows x d column-major, ld ldx), y and mu (nrows each) are uploaded once; problem b's
+ * rows are [row0[b], row0[b] + nrow[b]) of them.  Ranges may overlap or coincide (a multi-start
+ * aliases one range B times).  The batch owns all its device memory; an evaluation allocates
+ * nothing.  An sgp_batch is externally synchronised, like an sgp_ctx, and lives on one device.
+ *
+ * eval_vi: theta is P x B (column b = problem b, ld ldt), problem b's knots are m[b] x d
+ * column-major with ld m[b] at U + uoff[b]; grad is P x B with ld ldg (not read or written under
+ * SGP_FLAG_OBJ_ONLY, where it may be NULL).  active (B bytes, NULL = all): where active[b] == 0
+ * nothing of problem b is computed and nothing is written to its obj / grad / status or to its
+ * posterior state.  SGP_EINVAL before the first device call (sgp_diag_batch_args, sgp_diag.h, is
+ * the same check) for: a NULL pointer, B < 1, d outside [1, 32], nrow[b] < 1, a range leaving
+ * [0, nrows), ldx < nrows, an active m[b] outside [1, SGP_BATCH_MMAX], ldt or ldg < P, a kernel
+ * other than SGP_KERNEL_SQEXP / SGP_KERNEL_ARD (SGP_KERNEL_EXP is refused as sgp_predict refuses
+ * it), a non-finite delta or knot, and a theta entry that is not finite and positive.
+ * A problem whose K22 or K22 + K21 Z^-1 K12 is not positive definite does not fail the call:
+ * status[b] is the 1-based order of the first non-positive leading minor, positive for Sigma22
+ * (K22) and negative for K22 + K21 Z^-1 K12, its obj and grad are NaN, the other problems are
+ * unaffected, the call returns SGP_OK and sgp_last_error() names the first such problem (the
+ * per-candidate convention of sgp_vi_candidates).  status[b] = 0 otherwise.
+ * Every sum has a fixed order: a problem's obj, grad, status and posterior depend on its own rows,
+ * theta, U, m, delta and flags only -- not on B, its position, the other problems, `active` or
+ * the repeat -- bit for bit.
+ *
+ * posterior_u: the knot posterior (R/vi_functions.R:1161-1180) of each problem's last successful
+ * evaluation, as sgp_posterior_u gives it for a context; muu and u_mean are packed like U's
+ * columns (sum m_b values), u_var as m_b x m_b column-major blocks (sum m_b^2), with m_b the knot
+ * count of that evaluation; a problem that has none takes no entries (m_b = 0), and SGP_EINVAL
+ * when no problem has one.  set_data replaces y and mu (nrows values each) and drops the
+ * posteriors. */
+#define SGP_BATCH_MMAX 64
+typedef struct sgp_batch sgp_batch;
+int sgp_batch_create(sgp_batch** out, int device, const double* X, int64_t nrows, int64_t ldx,
+                     int d, const double* y, const double* mu, const int64_t* row0,
+                     const int64_t* nrow, int64_t B);
+int sgp_batch_destroy(sgp_batch* b);
+int sgp_batch_set_data(sgp_batch* b, const double* y, const double* mu);
+int sgp_batch_eval_vi(sgp_batch* b, int kernel, const double* theta, int64_t ldt, const double* U,
+                      const int64_t* uoff, const int64_t* m, double delta, unsigned flags,
+                      const unsigned char* active, double* obj, double* grad, int64_t ldg,
+                      int* status);
+int sgp_batch_posterior_u(sgp_batch* b, const double* muu, double* u_mean, double* u_var);
+
 /* Joint predictive scoring and draws from a Gaussian process: the branches of
  * the reference that use a full covariance -- my_nlp(mv = TRUE), my_nlp(family = "bernoulli",
  * mc = TRUE), my_kl(mv = TRUE) (R/evaluation_functions.R:21-26, 53-80, 120-133, 153-164) -- and the

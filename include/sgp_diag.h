@@ -124,6 +124,34 @@ int sgp_diag_predictor_run(struct sgp_predictor* p, int64_t chunk_rows, int rout
                            const double* x_pred, int64_t np, int64_t ldxp, const double* mu_pred,
                            double* pred_mean, double* pred_var, double* stage_ms);
 
+/* Host only (no device is touched): the argument checks of the batched VI path (sgp.h) -- the very
+ * functions sgp_batch_create (stage 0: the arguments up to B) and sgp_batch_eval_vi (stage 1:
+ * create's, then the rest) run before their first device call.  SGP_OK or SGP_EINVAL with
+ * sgp_last_error(). */
+int sgp_diag_batch_args(int stage, const double* X, int64_t nrows, int64_t ldx, int d,
+                        const double* y, const double* mu, const int64_t* row0,
+                        const int64_t* nrow, int64_t B, int kernel, const double* theta,
+                        int64_t ldt, const double* U, const int64_t* uoff, const int64_t* m,
+                        double delta, unsigned flags, const unsigned char* active,
+                        const double* obj, const double* grad, int64_t ldg, const int* status);
+
+/* Host only: the segment plan of a batch.  A segment is a run of at most SGP_BATCH_SEG_ROWS rows
+ * of one problem, counted from the problem's first row, so a problem's segments do not depend on
+ * the rest of the batch; both row passes run one workgroup per segment and the per-problem stages
+ * add the segments' records in this order.  *nseg = the number of segments; the first
+ * min(cap, *nseg) of them are written to seg_prob / seg_row0 / seg_rows (may be NULL with cap =
+ * 0); *seg_rows_max (or NULL) = SGP_BATCH_SEG_ROWS. */
+#define SGP_BATCH_SEG_ROWS 512
+int sgp_diag_batch_plan(const int64_t* row0, const int64_t* nrow, int64_t B, int64_t cap,
+                        int64_t* nseg, int64_t* seg_prob, int64_t* seg_row0, int64_t* seg_rows,
+                        int64_t* seg_rows_max);
+
+/* stage_ms (4 doubles, or NULL): the times by HIP events of row pass 1, the m x m stage, row pass 2
+ * and the finish of the batch's last evaluation (zeros when they were not recorded); enable != 0
+ * records them from the next evaluation on. */
+struct sgp_batch;
+int sgp_diag_batch_timing(struct sgp_batch* b, int enable, double* stage_ms);
+
 #ifdef __cplusplus
 }
 #endif

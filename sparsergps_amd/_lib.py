@@ -16,6 +16,9 @@ _lib = None
 
 c_double_p = C.POINTER(C.c_double)
 c_int_p = C.POINTER(C.c_int)
+c_int64_p = C.POINTER(C.c_int64)
+c_ubyte_p = C.POINTER(C.c_ubyte)
+SGP_BATCH_MMAX = 64   # sgp_batch_eval_vi's largest knot count
 
 SGP_OK, SGP_EINVAL, SGP_ENOTPD, SGP_EHIP, SGP_ENOMEM = 0, 1, 2, 3, 4
 KERNELS = {"sqexp": 0, "ard": 1, "exp": 2}
@@ -140,6 +143,24 @@ PROTOTYPES = {
     "sgp_diag_predictor_run": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, c_double_p, C.c_int64,
                                          C.c_int64, c_double_p, c_double_p, c_double_p,
                                          c_double_p]),
+    # the batched small-knot VI path (X, nrows, ldx, d, y, mu, row0, nrow, B, ...)
+    "sgp_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, c_double_p, C.c_int64, C.c_int64,
+                                   C.c_int, c_double_p, c_double_p, c_int64_p, c_int64_p,
+                                   C.c_int64]),
+    "sgp_batch_destroy": (C.c_int, [C.c_void_p]),
+    "sgp_batch_set_data": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
+    "sgp_batch_eval_vi": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_int64, c_double_p,
+                                    c_int64_p, c_int64_p, C.c_double, C.c_uint, c_ubyte_p,
+                                    c_double_p, c_double_p, C.c_int64, c_int_p]),
+    "sgp_batch_posterior_u": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    "sgp_diag_batch_args": (C.c_int, [C.c_int, c_double_p, C.c_int64, C.c_int64, C.c_int,
+                                      c_double_p, c_double_p, c_int64_p, c_int64_p, C.c_int64,
+                                      C.c_int, c_double_p, C.c_int64, c_double_p, c_int64_p,
+                                      c_int64_p, C.c_double, C.c_uint, c_ubyte_p, c_double_p,
+                                      c_double_p, C.c_int64, c_int_p]),
+    "sgp_diag_batch_plan": (C.c_int, [c_int64_p, c_int64_p, C.c_int64, C.c_int64, c_int64_p,
+                                      c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
+    "sgp_diag_batch_timing": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
     "sgp_sample_mvn": (C.c_int, [C.c_int, c_double_p, c_double_p, C.c_int64, C.c_int64, C.c_int64,
                                  C.c_uint64, c_double_p, C.c_int64]),
     "sgp_joint_nlp": (C.c_int, [C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, C.c_int64,

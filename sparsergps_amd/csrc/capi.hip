@@ -5240,4 +5240,414 @@ int sgp_diag_syrk_plan(int64_t n, int64_t m, int* plan, int* workgroups, double*
   return SGP_OK;
 }
 
+
+// ------------------------------------------------------------------------- batched VI
+// sgp_batch (include/sgp.h; k_batch.hip): B independent small-knot VI problems
+// on rows of one resident X / y / mu, four launches per evaluation of the whole batch.
+}  // extern "C"
+
+struct sgp_batch {
+  int device = 0, d = 0, pst = 0, post_stride = 0;
+  int64_t nrows = 0, B = 0, nseg = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  double *X = nullptr, *y = nullptr, *mu = nullptr, *par = nullptr, *rec1 = nullptr,
+         *rec2 = nullptr, *pm = nullptr, *sc = nullptr, *out = nullptr, *post = nullptr,
+         *res = nullptr;
+  int *seg_prob = nullptr, *seg_rows = nullptr;
+  int64_t* seg_row0 = nullptr;
+  double *h_par = nullptr, *h_out = nullptr;   // pinned
+  std::vector<int64_t> row0, nrow, seg0, nsegs, last_m;
+  std::vector<char> has_state;
+  int last_ard = 0;
+  float stage_ms[4] = {0.f, 0.f, 0.f, 0.f};
+  bool timing = false;
+};
+
+namespace {
+
+bool finite_all(const double* v, int64_t n, int64_t* bad) {
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) { *bad = i; return false; }
+  return true;
+}
+
+int batch_check_create(const double* X, int64_t nrows, int64_t ldx, int d, const double* y,
+                       const double* mu, const int64_t* row0, const int64_t* nrow, int64_t B) {
+  if (!X || !y || !mu || !row0 || !nrow) {
+    set_err("sgp_batch: X, y, mu, row0 and nrow must not be NULL");
+    return SGP_EINVAL;
+  }
+  if (B < 1 || B > INT32_MAX) { set_err("sgp_batch: B=%lld < 1", (long long)B); return SGP_EINVAL; }
+  if (d < 1 || d > SGP_MAXD) {
+    set_err("input dimension d=%d outside [1, %d]", d, SGP_MAXD);
+    return SGP_EINVAL;
+  }
+  if (nrows < 1 || ldx < nrows) {
+    set_err("sgp_batch: nrows=%lld, ldx=%lld (need nrows >= 1 and ldx >= nrows)", (long long)nrows,
+            (long long)ldx);
+    return SGP_EINVAL;
+  }
+  int64_t segs = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    if (nrow[b] < 1) {
+      set_err("sgp_batch: problem %lld has nrow=%lld < 1", (long long)b, (long long)nrow[b]);
+      return SGP_EINVAL;
+    }
+    if (row0[b] < 0 || row0[b] > nrows - nrow[b]) {
+      set_err("sgp_batch: problem %lld's rows [%lld, %lld) leave [0, %lld)", (long long)b,
+              (long long)row0[b], (long long)(row0[b] + nrow[b]), (long long)nrows);
+      return SGP_EINVAL;
+    }
+    segs += (nrow[b] + SGP_BATCH_SEG_ROWS - 1) / SGP_BATCH_SEG_ROWS;
+  }
+  if (segs > INT32_MAX / 2) { set_err("sgp_batch: too many segments"); return SGP_EINVAL; }
+  return SGP_OK;
+}
+
+int batch_check_eval(int d, int64_t B, int kernel, const double* theta, int64_t ldt,
+                     const double* U, const int64_t* uoff, const int64_t* m, double delta,
+                     unsigned flags, const unsigned char* active, const double* obj,
+                     const double* grad, int64_t ldg, const int* status) {
+  if (kernel == SGP_KERNEL_EXP) {
+    set_err("sgp_batch_eval_vi supports 'sqexp' and 'ard' (optimize_gp.R:263 rejects others)");
+    return SGP_EINVAL;
+  }
+  if (kernel != SGP_KERNEL_SQEXP && kernel != SGP_KERNEL_ARD) {
+    set_err("invalid covariance function (kernel=%d)", kernel);
+    return SGP_EINVAL;
+  }
+  const bool obj_only = flags & SGP_FLAG_OBJ_ONLY;
+  if (!theta || !U || !uoff || !m || !obj || !status || (!grad && !obj_only)) {
+    set_err("sgp_batch_eval_vi: theta, U, uoff, m, obj, status (and grad without "
+            "SGP_FLAG_OBJ_ONLY) must not be NULL");
+    return SGP_EINVAL;
+  }
+  const int P = num_ls(kernel, d) + 2;
+  if (ldt < P) { set_err("sgp_batch_eval_vi: ldt=%lld < P=%d", (long long)ldt, P); return SGP_EINVAL; }
+  if (grad && ldg < P) { set_err("sgp_batch_eval_vi: ldg=%lld < P=%d", (long long)ldg, P); return SGP_EINVAL; }
+  if (!std::isfinite(delta)) { set_err("sgp_batch_eval_vi: delta is not finite"); return SGP_EINVAL; }
+  for (int64_t b = 0; b < B; ++b) {
+    if (active && !active[b]) continue;
+    if (m[b] < 1 || m[b] > SGP_BATCH_MMAX) {
+      set_err("sgp_batch_eval_vi: problem %lld has m=%lld outside [1, %d]", (long long)b,
+              (long long)m[b], SGP_BATCH_MMAX);
+      return SGP_EINVAL;
+    }
+    if (uoff[b] < 0) {
+      set_err("sgp_batch_eval_vi: problem %lld has uoff=%lld < 0", (long long)b, (long long)uoff[b]);
+      return SGP_EINVAL;
+    }
+    const double* th = theta + b * ldt;
+    for (int p = 0; p < P; ++p)
+      if (!std::isfinite(th[p]) || !(th[p] > 0.0)) {
+        set_err("sgp_batch_eval_vi: problem %lld's theta[%d] = %g is not a positive finite number",
+                (long long)b, p, th[p]);
+        return SGP_EINVAL;
+      }
+    int64_t bad = 0;
+    if (!finite_all(U + uoff[b], m[b] * d, &bad)) {
+      set_err("sgp_batch_eval_vi: problem %lld's U[%lld, %lld] is not finite", (long long)b,
+              (long long)(bad % m[b]), (long long)(bad / m[b]));
+      return SGP_EINVAL;
+    }
+  }
+  return SGP_OK;
+}
+
+void batch_free(sgp_batch* b) {
+  (void)hipSetDevice(b->device);
+  if (b->stream) (void)hipStreamSynchronize(b->stream);
+  for (double* p : {b->X, b->y, b->mu, b->par, b->rec1, b->rec2, b->pm, b->sc, b->out, b->post,
+                    b->res})
+    if (p) (void)hipFree(p);
+  if (b->seg_prob) (void)hipFree(b->seg_prob);
+  if (b->seg_rows) (void)hipFree(b->seg_rows);
+  if (b->seg_row0) (void)hipFree(b->seg_row0);
+  if (b->h_par) (void)hipHostFree(b->h_par);
+  if (b->h_out) (void)hipHostFree(b->h_out);
+  for (hipEvent_t e : b->ev)
+    if (e) (void)hipEventDestroy(e);
+  if (b->stream) (void)hipStreamDestroy(b->stream);
+  delete b;
+}
+
+BatchArgs batch_args(const sgp_batch* b, int ard, int obj_only) {
+  BatchArgs a;
+  a.X = b->X; a.y = b->y; a.mu = b->mu; a.ldx = b->nrows;
+  a.par = b->par; a.pst = b->pst; a.d = b->d; a.ard = ard; a.obj_only = obj_only;
+  a.B = (int)b->B; a.nseg = (int)b->nseg;
+  a.seg_prob = b->seg_prob; a.seg_row0 = b->seg_row0; a.seg_rows = b->seg_rows;
+  a.rec1 = b->rec1; a.rec2 = b->rec2; a.pm = b->pm; a.sc = b->sc; a.out = b->out;
+  a.post = b->post; a.post_stride = b->post_stride;
+  return a;
+}
+
+int batch_create_impl(sgp_batch* b, const double* X, int64_t ldx, const double* y,
+                      const double* mu) {
+  const int64_t B = b->B, n = b->nrows;
+  const int d = b->d;
+  std::vector<int> sp, sr;
+  std::vector<int64_t> s0;
+  for (int64_t p = 0; p < B; ++p) {
+    b->seg0[(size_t)p] = (int64_t)sp.size();
+    for (int64_t r = 0; r < b->nrow[(size_t)p]; r += SGP_BATCH_SEG_ROWS) {
+      sp.push_back((int)p);
+      s0.push_back(b->row0[(size_t)p] + r);
+      sr.push_back((int)std::min<int64_t>(SGP_BATCH_SEG_ROWS, b->nrow[(size_t)p] - r));
+    }
+    b->nsegs[(size_t)p] = (int64_t)sp.size() - b->seg0[(size_t)p];
+  }
+  b->nseg = (int64_t)sp.size();
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+  for (hipEvent_t& e : b->ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipMalloc(&b->X, sizeof(double) * n * d));
+  HIPCHK(hipMalloc(&b->y, sizeof(double) * n));
+  HIPCHK(hipMalloc(&b->mu, sizeof(double) * n));
+  HIPCHK(hipMalloc(&b->par, sizeof(double) * B * b->pst));
+  HIPCHK(hipMalloc(&b->rec1, sizeof(double) * b->nseg * BATCH_REC1));
+  HIPCHK(hipMalloc(&b->rec2, sizeof(double) * b->nseg * BATCH_REC2));
+  HIPCHK(hipMalloc(&b->pm, sizeof(double) * B * BATCH_PM));
+  HIPCHK(hipMalloc(&b->sc, sizeof(double) * B * BATCH_SC));
+  HIPCHK(hipMalloc(&b->out, sizeof(double) * B * BATCH_OUT));
+  HIPCHK(hipMalloc(&b->post, sizeof(double) * B * b->post_stride));
+  HIPCHK(hipMalloc(&b->res, sizeof(double) * B * (BR_T + SGP_BATCH_MMAX)));
+  HIPCHK(hipMalloc(&b->seg_prob, sizeof(int) * b->nseg));
+  HIPCHK(hipMalloc(&b->seg_rows, sizeof(int) * b->nseg));
+  HIPCHK(hipMalloc(&b->seg_row0, sizeof(int64_t) * b->nseg));
+  HIPCHK(hipHostMalloc(&b->h_par, sizeof(double) * B * b->pst));
+  HIPCHK(hipHostMalloc(&b->h_out, sizeof(double) * B * BATCH_OUT));
+  HIPCHK(hipMemsetAsync(b->post, 0, sizeof(double) * B * b->post_stride, b->stream));
+  HIPCHK(hipMemsetAsync(b->out, 0, sizeof(double) * B * BATCH_OUT, b->stream));
+  HIPCHK(hipMemcpy2DAsync(b->X, sizeof(double) * n, X, sizeof(double) * ldx, sizeof(double) * n,
+                          (size_t)d, hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->y, y, sizeof(double) * n, hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->mu, mu, sizeof(double) * n, hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->seg_prob, sp.data(), sizeof(int) * sp.size(), hipMemcpyHostToDevice,
+                        b->stream));
+  HIPCHK(hipMemcpyAsync(b->seg_rows, sr.data(), sizeof(int) * sr.size(), hipMemcpyHostToDevice,
+                        b->stream));
+  HIPCHK(hipMemcpyAsync(b->seg_row0, s0.data(), sizeof(int64_t) * s0.size(),
+                        hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return SGP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sgp_diag_batch_args(int stage, const double* X, int64_t nrows, int64_t ldx, int d,
+                        const double* y, const double* mu, const int64_t* row0,
+                        const int64_t* nrow, int64_t B, int kernel, const double* theta,
+                        int64_t ldt, const double* U, const int64_t* uoff, const int64_t* m,
+                        double delta, unsigned flags, const unsigned char* active,
+                        const double* obj, const double* grad, int64_t ldg, const int* status) {
+  if (stage != 0 && stage != 1) { set_err("sgp_diag_batch_args: stage=%d", stage); return SGP_EINVAL; }
+  const int st = batch_check_create(X, nrows, ldx, d, y, mu, row0, nrow, B);
+  if (st != SGP_OK || stage == 0) return st;
+  return batch_check_eval(d, B, kernel, theta, ldt, U, uoff, m, delta, flags, active, obj, grad,
+                          ldg, status);
+}
+
+int sgp_diag_batch_plan(const int64_t* row0, const int64_t* nrow, int64_t B, int64_t cap,
+                        int64_t* nseg, int64_t* seg_prob, int64_t* seg_row0, int64_t* seg_rows,
+                        int64_t* seg_rows_max) {
+  if (!row0 || !nrow || B < 1 || !nseg || cap < 0 ||
+      (cap > 0 && (!seg_prob || !seg_row0 || !seg_rows))) {
+    set_err("invalid sgp_diag_batch_plan arguments");
+    return SGP_EINVAL;
+  }
+  int64_t k = 0;
+  for (int64_t p = 0; p < B; ++p) {
+    if (nrow[p] < 1 || row0[p] < 0) {
+      set_err("sgp_diag_batch_plan: problem %lld has row0=%lld, nrow=%lld", (long long)p,
+              (long long)row0[p], (long long)nrow[p]);
+      return SGP_EINVAL;
+    }
+    for (int64_t r = 0; r < nrow[p]; r += SGP_BATCH_SEG_ROWS, ++k)
+      if (k < cap) {
+        seg_prob[k] = p;
+        seg_row0[k] = row0[p] + r;
+        seg_rows[k] = std::min<int64_t>(SGP_BATCH_SEG_ROWS, nrow[p] - r);
+      }
+  }
+  *nseg = k;
+  if (seg_rows_max) *seg_rows_max = SGP_BATCH_SEG_ROWS;
+  return SGP_OK;
+}
+
+int sgp_batch_create(sgp_batch** out, int device, const double* X, int64_t nrows, int64_t ldx,
+                     int d, const double* y, const double* mu, const int64_t* row0,
+                     const int64_t* nrow, int64_t B) {
+  if (!out) { set_err("sgp_batch_create: out is NULL"); return SGP_EINVAL; }
+  *out = nullptr;
+  const int st = batch_check_create(X, nrows, ldx, d, y, mu, row0, nrow, B);
+  if (st != SGP_OK) return st;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+    (void)hipGetLastError();
+    set_err("sgp_batch_create: no HIP device visible (there is no CPU path)");
+    return SGP_EHIP;
+  }
+  if (device < 0 || device >= ndev) {
+    set_err("sgp_batch_create: device %d, but %d device(s) are visible", device, ndev);
+    return SGP_EINVAL;
+  }
+  sgp_batch* b = new sgp_batch;
+  b->device = device;
+  b->d = d;
+  b->nrows = nrows;
+  b->B = B;
+  b->pst = BP_U + SGP_BATCH_MMAX * d;
+  b->post_stride = BR_T + SGP_BATCH_MMAX + b->pst;
+  b->row0.assign(row0, row0 + B);
+  b->nrow.assign(nrow, nrow + B);
+  b->seg0.assign((size_t)B, 0);
+  b->nsegs.assign((size_t)B, 0);
+  b->last_m.assign((size_t)B, 0);
+  b->has_state.assign((size_t)B, 0);
+  const int cst = batch_create_impl(b, X, ldx, y, mu);
+  if (cst != SGP_OK) {
+    const std::string keep = g_err;
+    batch_free(b);
+    g_err = keep;
+    return cst;
+  }
+  *out = b;
+  return SGP_OK;
+}
+
+int sgp_batch_destroy(sgp_batch* b) {
+  if (!b) { set_err("sgp_batch_destroy: the sgp_batch is NULL"); return SGP_EINVAL; }
+  batch_free(b);
+  return SGP_OK;
+}
+
+int sgp_batch_set_data(sgp_batch* b, const double* y, const double* mu) {
+  if (!b) { set_err("sgp_batch_set_data: the sgp_batch is NULL"); return SGP_EINVAL; }
+  if (!y || !mu) { set_err("sgp_batch_set_data: y and mu must not be NULL"); return SGP_EINVAL; }
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipMemcpyAsync(b->y, y, sizeof(double) * b->nrows, hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->mu, mu, sizeof(double) * b->nrows, hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  std::fill(b->has_state.begin(), b->has_state.end(), 0);   // the posteriors were of the old data
+  HIPCHK(hipMemsetAsync(b->post, 0, sizeof(double) * b->B * b->post_stride, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return SGP_OK;
+}
+
+int sgp_batch_eval_vi(sgp_batch* b, int kernel, const double* theta, int64_t ldt, const double* U,
+                      const int64_t* uoff, const int64_t* m, double delta, unsigned flags,
+                      const unsigned char* active, double* obj, double* grad, int64_t ldg,
+                      int* status) {
+  if (!b) { set_err("sgp_batch_eval_vi: the sgp_batch is NULL"); return SGP_EINVAL; }
+  const int cst = batch_check_eval(b->d, b->B, kernel, theta, ldt, U, uoff, m, delta, flags,
+                                   active, obj, grad, ldg, status);
+  if (cst != SGP_OK) return cst;
+  const int d = b->d, ard = kernel == SGP_KERNEL_ARD, L = ard ? d : 1, P = L + 2;
+  const bool obj_only = flags & SGP_FLAG_OBJ_ONLY;
+  bool any = false;
+  for (int64_t p = 0; p < b->B; ++p) {
+    double* h = b->h_par + p * b->pst;
+    const bool on = !active || active[p];
+    h[BP_ACTIVE] = on ? 1.0 : 0.0;
+    if (!on) continue;
+    any = true;
+    const double* th = theta + p * ldt;
+    const double tau2 = th[L + 1] * th[L + 1];
+    h[BP_M] = (double)m[p];
+    h[BP_SIG2] = th[0] * th[0];
+    h[BP_TAU2] = tau2;
+    h[BP_Z] = tau2 + delta;
+    h[BP_DELTA] = delta;
+    h[BP_NROW] = (double)b->nrow[(size_t)p];
+    h[BP_RDET] = (flags & SGP_FLAG_R_DET) ? 1.0 : 0.0;
+    h[BP_SEG0] = (double)b->seg0[(size_t)p];
+    h[BP_NSEG] = (double)b->nsegs[(size_t)p];
+    for (int c = 0; c < d; ++c) h[BP_RL + c] = 1.0 / th[1 + (ard ? c : 0)];
+    const double* u = U + uoff[p];
+    for (int c = 0; c < d; ++c)
+      for (int j = 0; j < SGP_BATCH_MMAX; ++j)
+        h[BP_U + c * SGP_BATCH_MMAX + j] = j < m[p] ? u[(int64_t)c * m[p] + j] : 0.0;
+  }
+  if (!any) return SGP_OK;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipMemcpyAsync(b->par, b->h_par, sizeof(double) * b->B * b->pst, hipMemcpyHostToDevice,
+                        b->stream));
+  const BatchArgs a = batch_args(b, ard, obj_only ? 1 : 0);
+  HIPCHK(launch_batch_eval(a, b->stream, b->timing ? b->ev : nullptr));
+  HIPCHK(hipMemcpyAsync(b->h_out, b->out, sizeof(double) * b->B * BATCH_OUT,
+                        hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (b->timing)
+    for (int q = 0; q < 4; ++q) HIPCHK(hipEventElapsedTime(&b->stage_ms[q], b->ev[q], b->ev[q + 1]));
+  b->last_ard = ard;
+  bool failed = false;
+  for (int64_t p = 0; p < b->B; ++p) {
+    if (active && !active[p]) continue;
+    const double* o = b->h_out + p * BATCH_OUT;
+    const int st = (int)o[1];
+    status[p] = st;
+    if (st) {
+      obj[p] = NAN;
+      if (grad)
+        for (int q = 0; q < P; ++q) grad[p * ldg + q] = NAN;
+      if (!failed)
+        set_err("problem %lld: chol(): the leading minor of order %d of %s is not positive definite",
+                (long long)p, st > 0 ? st : -st,
+                st > 0 ? "Sigma22" : "Sigma22 + t(Sigma12) %*% ZSig12");
+      failed = true;
+      continue;
+    }
+    obj[p] = o[0];
+    if (!obj_only)
+      for (int q = 0; q < P; ++q) grad[p * ldg + q] = o[2 + q];
+    b->has_state[(size_t)p] = 1;
+    b->last_m[(size_t)p] = m[p];
+  }
+  return SGP_OK;
+}
+
+int sgp_batch_posterior_u(sgp_batch* b, const double* muu, double* u_mean, double* u_var) {
+  if (!b) { set_err("sgp_batch_posterior_u: the sgp_batch is NULL"); return SGP_EINVAL; }
+  if (!muu || !u_mean || !u_var) {
+    set_err("sgp_batch_posterior_u: muu, u_mean and u_var must not be NULL");
+    return SGP_EINVAL;
+  }
+  if (std::find(b->has_state.begin(), b->has_state.end(), (char)1) == b->has_state.end()) {
+    set_err("sgp_batch_posterior_u: no problem of the batch has a successful evaluation");
+    return SGP_EINVAL;
+  }
+  HIPCHK(hipSetDevice(b->device));
+  const int64_t rs = BR_T + SGP_BATCH_MMAX;
+  std::vector<double> h((size_t)(b->B * rs));
+  HIPCHK(launch_batch_post(batch_args(b, b->last_ard, 0), b->res, b->stream));
+  HIPCHK(hipMemcpyAsync(h.data(), b->res, sizeof(double) * h.size(), hipMemcpyDeviceToHost,
+                        b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  int64_t o1 = 0, o2 = 0;
+  for (int64_t p = 0; p < b->B; ++p) {
+    const int64_t m = b->has_state[(size_t)p] ? b->last_m[(size_t)p] : 0;   // none: no entries
+    const double* r = h.data() + p * rs;
+    for (int64_t j = 0; j < m; ++j) u_mean[o1 + j] = muu[o1 + j] + r[BR_T + j];
+    for (int64_t j = 0; j < m; ++j)
+      for (int64_t i = 0; i < m; ++i) u_var[o2 + i + j * m] = r[i * SGP_BATCH_MMAX + j];
+    o1 += m;
+    o2 += m * m;
+  }
+  return SGP_OK;
+}
+
+/* stage_ms (4 floats as doubles): HIP-event times of pass 1, the m x m stage, pass 2 and the finish
+ * of the last evaluation; enable = 1 records the events from the next evaluation on. */
+int sgp_diag_batch_timing(sgp_batch* b, int enable, double* stage_ms) {
+  if (!b) { set_err("sgp_diag_batch_timing: the sgp_batch is NULL"); return SGP_EINVAL; }
+  if (stage_ms)
+    for (int q = 0; q < 4; ++q) stage_ms[q] = b->timing ? (double)b->stage_ms[q] : 0.0;
+  b->timing = enable != 0;
+  return SGP_OK;
+}
+
 }  // extern "C"

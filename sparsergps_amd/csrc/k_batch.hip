@@ -1,0 +1,641 @@
+// Batched small-knot Titsias-VI evaluation (sgp_batch_eval_vi): B independent
+// problems, each with its own rows, theta and m <= 64 knots, in four launches for the whole batch.
+// Per problem the semantics are sgp_eval_vi's (elbo_fun R/vi_functions.R:64-121, trace_term_fun
+// l.14-27, delbo_dcov_par l.126-419):
+//   S = K^T K, t = K^T r, r^T r                                  k_batch_pass1, per segment
+//   K22 = Kuu + delta I, Bm = K22 + S / z, their inverses and log-dets, u = Bm^-1 t / z,
+//   P' = K22^-1 / tau^2 - Bm^-1 / z - u u^T / z, the objective, the G22 : dK22 terms
+//                                                                k_batch_mm, per problem, in LDS
+//   G = (r / z) u^T + K P', W = G o K, sum W dK/dlog theta       k_batch_pass2, per segment
+//   the gradient                                                 k_batch_finish, per problem
+// A segment is a run of at most SGP_BATCH_SEG_ROWS rows of one problem, counted from the problem's
+// first row, so a problem's segments do not depend on what else the batch holds.  A workgroup of
+// four waves takes 64 rows per step and forms k in registers in an operand layout of
+// v_mfma_f64_16x16x4_f64: pass 1 with lane l on knot 16 b + (l & 15) and rows 4 q + (l >> 4) (k
+// is then both operands of S += k k^T, and only the nb (nb + 1) / 2 block pairs are formed), pass
+// 2 with lane l on row l & 15 and knots 4 s + (l >> 4), the layout of k_fit_scan, whose result
+// layout meets it again for W = G o K.  Every sum has a fixed order, no kernel uses atomics, and
+// nothing a problem computes reads another problem's data: results are bit-identical whatever
+// the batch, the position, `active` or the repeat.
+#include <math.h>
+
+#include "sgp_internal.h"
+
+namespace {
+
+constexpr int MM = SGP_BATCH_MMAX;   // 64: the LDS matrices' row stride
+
+// sum of v over the 256 threads in a fixed tree order; red: 256 doubles
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  red[tid] = v;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st) red[tid] += red[tid + st];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// sum of rec[q * stride], q = 0 .. n - 1, in that order; the loads go out eight at a time
+__device__ __forceinline__ double rec_sum(const double* __restrict__ rec, int64_t stride, int n) {
+  double s = 0.0;
+  int q = 0;
+  for (; q + 8 <= n; q += 8) {
+    double v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = rec[(q + k) * stride];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += v[k];
+  }
+  for (; q < n; ++q) s += rec[q * stride];
+  return s;
+}
+
+// ------------------------------------------------------------------------------ row pass 1
+template <int NT>
+__device__ __forceinline__ void pass1_body(const BatchArgs& a, const double* __restrict__ P,
+                                           int64_t row0, int rows, double* __restrict__ rec,
+                                           double* lds, double* tw, double* rrs, double* rl_s) {
+  constexpr int Mp = 16 * NT;
+  const int d = a.d, m = (int)P[BP_M];
+  const double sig2 = P[BP_SIG2];
+  double* u_s = lds;             // [c][Mp]
+  double* xs = lds + d * MM;     // [c][64]
+  double* rs = rrs + 64;         // 64: this step's r
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, g = lane >> 4;
+
+  for (int q = tid; q < d * Mp; q += 256) {
+    const int c = q / Mp, j = q - c * Mp;
+    u_s[c * Mp + j] = P[BP_U + c * MM + j];
+  }
+  for (int q = tid; q < d; q += 256) rl_s[q] = P[BP_RL + q];
+
+  d4 acc[NT * (NT + 1) / 2];
+#pragma unroll
+  for (int p = 0; p < NT * (NT + 1) / 2; ++p) acc[p] = d4{0.0, 0.0, 0.0, 0.0};
+  double tacc[NT];
+#pragma unroll
+  for (int b = 0; b < NT; ++b) tacc[b] = 0.0;
+  double rracc = 0.0;
+
+  for (int step = 0; step * 64 < rows; ++step) {
+    __syncthreads();   // the staging above / the previous step's reads of xs and rs
+    for (int q = tid; q < d * 64; q += 256) {
+      const int c = q >> 6, i = q & 63;
+      const int row = step * 64 + i;
+      xs[q] = row < rows ? a.X[(int64_t)c * a.ldx + row0 + row] : 0.0;
+    }
+    if (tid < 64) {
+      const int row = step * 64 + tid;
+      const double r = row < rows ? a.y[row0 + row] - a.mu[row0 + row] : 0.0;
+      rs[tid] = r;
+      rracc = fma(r, r, rracc);
+    }
+    __syncthreads();
+
+    double kf[NT][4];
+#pragma unroll
+    for (int b = 0; b < NT; ++b)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) kf[b][q] = 0.0;
+    const double* xr = xs + wv * 16 + g;
+    for (int c = 0; c < d; ++c) {
+      const double rl = rl_s[c];
+      double xv[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) xv[q] = xr[c * 64 + 4 * q];
+#pragma unroll
+      for (int b = 0; b < NT; ++b) {
+        const double uv = u_s[c * Mp + 16 * b + r16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const double t = (xv[q] - uv) * rl;   // the raw difference first
+          kf[b][q] = fma(t, t, kf[b][q]);
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < NT; ++b) {
+      const bool jv = 16 * b + r16 < m;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const bool iv = step * 64 + wv * 16 + 4 * q + g < rows;
+        const double v = sig2 * sgp_exp_nonpos(-0.5 * kf[b][q]);
+        kf[b][q] = (jv && iv) ? v : 0.0;
+        tacc[b] = fma(kf[b][q], rs[wv * 16 + 4 * q + g], tacc[b]);
+      }
+    }
+    // S[16 bi + i][16 bj + j] += sum over the wave's 16 rows: A[i][row] = B[row][j] = k
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      int p = 0;
+#pragma unroll
+      for (int bi = 0; bi < NT; ++bi)
+#pragma unroll
+        for (int bj = bi; bj < NT; ++bj, ++p)
+          acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(kf[bi][q], kf[bj][q], acc[p], 0, 0, 0);
+    }
+  }
+
+  // the four waves' partial S, added in wave order into LDS (over the dead knots and rows)
+  for (int w = 0; w < 4; ++w) {
+    __syncthreads();
+    if (wv == w) {
+      int p = 0;
+#pragma unroll
+      for (int bi = 0; bi < NT; ++bi)
+#pragma unroll
+        for (int bj = bi; bj < NT; ++bj, ++p)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            double* s = lds + (16 * bi + 4 * r + g) * MM + 16 * bj + r16;
+            *s = w ? *s + acc[p][r] : acc[p][r];
+          }
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < NT; ++b) {
+    double t = tacc[b];
+    t += __shfl_xor(t, 16, 64);
+    t += __shfl_xor(t, 32, 64);
+    if (g == 0) tw[wv * MM + 16 * b + r16] = t;
+  }
+  if (tid < 64) rrs[tid] = rracc;
+  __syncthreads();
+  for (int q = tid; q < Mp * Mp; q += 256) {
+    const int i = q / Mp, j = q - i * Mp;
+    rec[i * MM + j] = (i >> 4) > (j >> 4) ? lds[j * MM + i] : lds[i * MM + j];
+  }
+  if (tid < Mp) rec[BR_T + tid] = ((tw[tid] + tw[MM + tid]) + tw[2 * MM + tid]) + tw[3 * MM + tid];
+  if (tid == 0) {
+    double rr = 0.0;
+    for (int q = 0; q < 64; ++q) rr += rrs[q];
+    rec[BR_RR] = rr;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_batch_pass1(BatchArgs a) {
+  __shared__ __attribute__((aligned(16))) double lds[MM * MM];
+  __shared__ double tw[4 * MM], rrs[128], rl_s[SGP_MAXD];
+  const int seg = blockIdx.x;
+  const int prob = a.seg_prob[seg];
+  const double* P = a.par + (int64_t)prob * a.pst;
+  if (P[BP_ACTIVE] == 0.0) return;
+  const int64_t row0 = a.seg_row0[seg];
+  const int rows = a.seg_rows[seg];
+  double* rec = a.rec1 + (int64_t)seg * BATCH_REC1;
+  switch (((int)P[BP_M] + 15) >> 4) {
+    case 1: pass1_body<1>(a, P, row0, rows, rec, lds, tw, rrs, rl_s); break;
+    case 2: pass1_body<2>(a, P, row0, rows, rec, lds, tw, rrs, rl_s); break;
+    case 3: pass1_body<3>(a, P, row0, rows, rec, lds, tw, rrs, rl_s); break;
+    default: pass1_body<4>(a, P, row0, rows, rec, lds, tw, rrs, rl_s); break;
+  }
+}
+
+// ------------------------------------------------------------------------------ m x m stage
+// The sweep operator on the leading m x m of A (row stride 64, in LDS): after the m sweeps A holds
+// -A^-1.  On an SPD matrix the pivot of sweep k is the ratio of the leading minors of order k + 1
+// and k (the square of Cholesky's k-th diagonal), so the first pivot that is not positive gives
+// chol()'s "leading minor of order k + 1".  Returns 0 or that order; *ld = the log-determinant.
+__device__ int sweep_spd(double* A, int m, double* ck, double* ld) {
+  const int tid = threadIdx.x;
+  double l = 0.0;
+  for (int k = 0; k < m; ++k) {
+    __syncthreads();
+    const double dk = A[k * MM + k];
+    if (!(dk > 0.0)) return k + 1;
+    l += log(dk);
+    if (tid < m) ck[tid] = A[tid * MM + k];   // = row k: A stays symmetric
+    __syncthreads();
+    const double rd = 1.0 / dk;
+    for (int e = tid; e < m * MM; e += 256) {
+      const int i = e >> 6, j = e & (MM - 1);
+      if (j >= m) continue;
+      double v;
+      if (i == k) v = j == k ? -rd : ck[j] * rd;
+      else if (j == k) v = ck[i] * rd;
+      else v = A[i * MM + j] - ck[i] * (ck[j] * rd);
+      A[i * MM + j] = v;
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < m * MM; e += 256) {
+    const int i = e >> 6, j = e & (MM - 1);
+    if (j >= m) continue;
+    A[i * MM + j] = -A[i * MM + j];
+  }
+  __syncthreads();
+  *ld = l;
+  return 0;
+}
+
+// (U_i - U_j) scaled, squared and summed: the exponent's -2 x
+__device__ __forceinline__ double knot_dist2(const double* __restrict__ P, int d, int i, int j) {
+  double s = 0.0;
+  for (int c = 0; c < d; ++c) {
+    const double t = (P[BP_U + c * MM + i] - P[BP_U + c * MM + j]) * P[BP_RL + c];
+    s = fma(t, t, s);
+  }
+  return s;
+}
+
+__global__ void __launch_bounds__(256) k_batch_mm(BatchArgs a) {
+  __shared__ __attribute__((aligned(16))) double A[MM * MM], Bm[MM * MM], S[MM * MM], T[MM * MM];
+  __shared__ double t_s[MM], u_s[MM], ck[MM], red[256];
+  const int prob = blockIdx.x, tid = threadIdx.x;
+  const double* P = a.par + (int64_t)prob * a.pst;
+  if (P[BP_ACTIVE] == 0.0) return;
+  const int d = a.d, m = (int)P[BP_M];
+  const double sig2 = P[BP_SIG2], tau2 = P[BP_TAU2], z = P[BP_Z], delta = P[BP_DELTA];
+  const double n = P[BP_NROW];
+  const int seg0 = (int)P[BP_SEG0], nseg = (int)P[BP_NSEG];
+  double* out = a.out + (int64_t)prob * BATCH_OUT;
+  double* sc = a.sc + (int64_t)prob * BATCH_SC;
+
+  // the segment records, in segment order
+  for (int e = tid; e < m * MM; e += 256) {
+    const int i = e >> 6, j = e & (MM - 1);
+    if (j >= m) continue;
+    const double s = rec_sum(a.rec1 + (int64_t)seg0 * BATCH_REC1 + i * MM + j, BATCH_REC1, nseg);
+    S[i * MM + j] = s;
+    const double kuu = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j));
+    const double k22 = kuu + (i == j ? delta : 0.0);
+    A[i * MM + j] = k22;
+    Bm[i * MM + j] = k22 + s / z;
+  }
+  if (tid < m) t_s[tid] = rec_sum(a.rec1 + (int64_t)seg0 * BATCH_REC1 + BR_T + tid, BATCH_REC1, nseg);
+  const double rr = rec_sum(a.rec1 + (int64_t)seg0 * BATCH_REC1 + BR_RR, BATCH_REC1, nseg);
+
+  double ld22 = 0.0, ldB = 0.0;
+  int st = sweep_spd(A, m, ck, &ld22);
+  if (!st) st = -sweep_spd(Bm, m, ck, &ldB);
+  if (st) {
+    if (tid == 0) {
+      out[0] = NAN;
+      out[1] = (double)st;
+    }
+    return;
+  }
+  // A = K22^-1, Bm = Bm^-1
+  if (tid < m) {
+    double s = 0.0;
+    for (int k = 0; k < m; ++k) s = fma(Bm[tid * MM + k], t_s[k], s);
+    u_s[tid] = s / z;
+  }
+  __syncthreads();
+  double su = 0.0;
+  if (tid < m)
+    for (int k = 0; k < m; ++k) su = fma(S[tid * MM + k], u_s[k], su);
+  const double tu = block_sum(tid < m ? t_s[tid] * u_s[tid] : 0.0, red);
+  const double uSu = block_sum(tid < m ? u_s[tid] * su : 0.0, red);
+  double p1 = 0.0, p2 = 0.0;
+  for (int e = tid; e < m * MM; e += 256) {
+    const int i = e >> 6, j = e & (MM - 1);
+    if (j >= m) continue;
+    p1 = fma(A[i * MM + j], S[i * MM + j], p1);
+    p2 = fma(Bm[i * MM + j], S[i * MM + j], p2);
+  }
+  const double trKS = block_sum(p1, red);
+  const double trBS = block_sum(p2, red);
+
+  // elbo_fun (vi_functions.R:102-118)
+  const double quad = -0.5 * rr / z + 0.5 * tu / z;
+  const double logdet22 = P[BP_RDET] != 0.0 ? log(exp(ld22)) : ld22;
+  const double det_part = -0.5 * (n * log(z) - logdet22 + ldB);
+  const double trace_term = -(1.0 / (2.0 * tau2)) * (n * (sig2 + delta) - trKS);
+  if (tid == 0) {
+    out[0] = quad + det_part - (n / 2.0) * log(2.0 * M_PI) + trace_term;
+    out[1] = 0.0;
+    sc[BS_TRACE] = trace_term;
+    sc[BS_TRBS] = trBS;
+    sc[BS_ATA] = (rr - 2.0 * tu + uSu) / (z * z);
+  }
+  // what sgp_batch_posterior_u needs: Bm^-1, u and the problem's parameters and knots
+  double* post = a.post + (int64_t)prob * a.post_stride;
+  for (int e = tid; e < m * MM; e += 256) {
+    const int i = e >> 6, j = e & (MM - 1);
+    if (j >= m) continue;
+    post[i * MM + j] = Bm[i * MM + j];
+  }
+  if (tid < m) post[MM * MM + tid] = u_s[tid];
+  for (int q = tid; q < a.pst; q += 256) post[MM * MM + MM + q] = P[q];
+  if (a.obj_only) return;
+
+  double* pm = a.pm + (int64_t)prob * BATCH_PM;
+  for (int e = tid; e < m * MM; e += 256) {
+    const int i = e >> 6, j = e & (MM - 1);
+    if (j >= m) continue;
+    pm[i * MM + j] = A[i * MM + j] / tau2 - Bm[i * MM + j] / z - u_s[i] * u_s[j] / z;
+  }
+  if (tid < m) {
+    pm[BPM_U + tid] = u_s[tid];
+    pm[BPM_KD + tid] = A[tid * MM + tid];
+  }
+  // G22 = -1/2 u u^T + 1/2 (K22^-1 - Bm^-1) - K22^-1 S K22^-1 / (2 tau^2), contracted with
+  // dK22 / dlog theta (sigma: 2 Kuu; l: Kuu |D|^2 / l^2; l_c: Kuu (D_c / l_c)^2; tau: none)
+  for (int e = tid; e < m * MM; e += 256) {
+    const int i = e >> 6, j = e & (MM - 1);
+    if (j >= m) continue;
+    double s = 0.0;
+    for (int k = 0; k < m; ++k) s = fma(A[i * MM + k], S[k * MM + j], s);
+    T[i * MM + j] = s;
+  }
+  __syncthreads();
+  for (int e = tid; e < m * MM; e += 256) {
+    const int i = e >> 6, j = e & (MM - 1);
+    if (j >= m) continue;
+    double s = 0.0;
+    for (int k = 0; k < m; ++k) s = fma(T[i * MM + k], A[k * MM + j], s);
+    const double g22 = -0.5 * u_s[i] * u_s[j] + 0.5 * (A[i * MM + j] - Bm[i * MM + j]) -
+                       s / (2.0 * tau2);
+    const double kuu = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j));
+    Bm[i * MM + j] = g22 * kuu;   // H: each thread rewrites only the entries it read
+  }
+  __syncthreads();
+  double h = 0.0;
+  for (int e = tid; e < m * MM; e += 256)
+    if ((e & (MM - 1)) < m) h += Bm[e];
+  const double hs = block_sum(h, red);
+  if (tid == 0) sc[BS_G22] = 2.0 * hs;
+  if (a.ard) {
+    for (int c = 0; c < d; ++c) {
+      double v = 0.0;
+      for (int e = tid; e < m * MM; e += 256) {
+        const int i = e >> 6, j = e & (MM - 1);
+        if (j >= m) continue;
+        const double t = (P[BP_U + c * MM + i] - P[BP_U + c * MM + j]) * P[BP_RL + c];
+        v = fma(Bm[i * MM + j], t * t, v);
+      }
+      const double vs = block_sum(v, red);
+      if (tid == 0) sc[BS_G22 + 1 + c] = vs;
+    }
+  } else {
+    double v = 0.0;
+    for (int e = tid; e < m * MM; e += 256) {
+      const int i = e >> 6, j = e & (MM - 1);
+      if (j >= m) continue;
+      v = fma(Bm[i * MM + j], knot_dist2(P, d, i, j), v);
+    }
+    const double vs = block_sum(v, red);
+    if (tid == 0) sc[BS_G22 + 1] = vs;
+  }
+}
+
+// ------------------------------------------------------------------------------ row pass 2
+template <int NT, bool ARD>
+__device__ __forceinline__ void pass2_body(const BatchArgs& a, const double* __restrict__ P,
+                                           const double* __restrict__ pm, int64_t row0, int rows,
+                                           double* __restrict__ rec, double* xu_s, double* pp_s,
+                                           double* vec_s, double* xs, double* red, double* el_s) {
+  constexpr int Mp = 16 * NT, SN = 4 * NT;
+  const int d = a.d, m = (int)P[BP_M];
+  const double sig2 = P[BP_SIG2], rz = 1.0 / P[BP_Z];
+  double* u_s = vec_s;             // [g][s]
+  double* kd_s = vec_s + MM;       // [g][s]: the diagonal of K22^-1
+  double* rs = vec_s + 2 * MM;     // 64: r / z of this step's rows
+  double* rl_s = vec_s + 3 * MM;   // d
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, g = lane >> 4;
+
+  for (int q = tid; q < d * Mp; q += 256) {
+    const int c = q / Mp, j = q - c * Mp;
+    xu_s[(c * 4 + (j & 3)) * SN + (j >> 2)] = P[BP_U + c * MM + j];
+  }
+  for (int q = tid; q < Mp * Mp; q += 256) {
+    const int i = q / Mp, j = q - i * Mp;
+    pp_s[q] = (i < m && j < m) ? pm[i * MM + j] : 0.0;
+  }
+  for (int q = tid; q < Mp; q += 256) {
+    u_s[(q & 3) * SN + (q >> 2)] = q < m ? pm[BPM_U + q] : 0.0;
+    kd_s[(q & 3) * SN + (q >> 2)] = q < m ? pm[BPM_KD + q] : 0.0;
+  }
+  for (int q = tid; q < d; q += 256) rl_s[q] = P[BP_RL + q];
+  if (ARD)
+    for (int c = 0; c < d; ++c) el_s[c * 256 + tid] = 0.0;
+
+  double esig = 0.0, el = 0.0, csum = 0.0, ccnt = 0.0, cdg = 0.0;
+  for (int step = 0; step * 64 < rows; ++step) {
+    __syncthreads();
+    for (int q = tid; q < d * 64; q += 256) {
+      const int c = q >> 6, i = q & 63;
+      const int row = step * 64 + i;
+      xs[q] = row < rows ? a.X[(int64_t)c * a.ldx + row0 + row] : 0.0;
+    }
+    if (tid < 64) {
+      const int row = step * 64 + tid;
+      rs[tid] = row < rows ? (a.y[row0 + row] - a.mu[row0 + row]) * rz : 0.0;
+    }
+    __syncthreads();
+
+    const bool iv = step * 64 + wv * 16 + r16 < rows;
+    const double* xr = xs + wv * 16 + r16;
+    double e2[SN], kf[SN];
+#pragma unroll
+    for (int s = 0; s < SN; ++s) e2[s] = 0.0;
+    for (int c = 0; c < d; ++c) {
+      const double xc = xr[c * 64], rl = rl_s[c];
+      const double* u = xu_s + (c * 4 + g) * SN;
+#pragma unroll
+      for (int s = 0; s < SN; ++s) {
+        const double t = (xc - u[s]) * rl;   // the raw difference first: coincidence stays exact
+        e2[s] = fma(t, t, e2[s]);
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < SN; ++s) {
+      const double v = sig2 * sgp_exp_nonpos(-0.5 * e2[s]);
+      kf[s] = (iv && 4 * s + g < m) ? v : 0.0;
+    }
+    d4 acc[NT];
+#pragma unroll
+    for (int cb = 0; cb < NT; ++cb) acc[cb] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < SN; ++s)
+#pragma unroll
+      for (int cb = 0; cb < NT; ++cb)
+        acc[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(pp_s[(4 * s + g) * Mp + 16 * cb + r16],
+                                                       kf[s], acc[cb], 0, 0, 0);
+    const double ri = rs[wv * 16 + r16];
+    double w[SN];
+#pragma unroll
+    for (int cb = 0; cb < NT; ++cb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int s = 4 * cb + r;
+        const double gv = fma(ri, u_s[g * SN + s], acc[cb][r]);   // G = (r / z) u^T + K P'
+        w[s] = gv * kf[s];
+        esig += w[s];
+        if (!ARD) el = fma(w[s], e2[s], el);
+        // quirk Q5: the tau derivative of a pair whose raw differences are all zero
+        if (e2[s] == 0.0 && iv && 4 * s + g < m) {
+          csum += gv;
+          ccnt += 1.0;
+          cdg += kd_s[g * SN + s];
+        }
+      }
+    if (ARD)
+      for (int c = 0; c < d; ++c) {
+        const double xc = xr[c * 64], rl = rl_s[c];
+        const double* u = xu_s + (c * 4 + g) * SN;
+        double v = 0.0;
+#pragma unroll
+        for (int s = 0; s < SN; ++s) {
+          const double t = (xc - u[s]) * rl;
+          v = fma(w[s], t * t, v);
+        }
+        el_s[c * 256 + tid] += v;   // the thread's own slot
+      }
+  }
+
+  const double e0 = block_sum(esig, red);
+  const double e1 = block_sum(csum, red);
+  const double e2s = block_sum(ccnt, red);
+  const double e3 = block_sum(cdg, red);
+  const int L = ARD ? d : 1;
+  if (ARD) {
+    for (int st = 128; st > 0; st >>= 1) {
+      __syncthreads();
+      for (int q = tid; q < d * st; q += 256) {
+        const int c = q / st, i = q - c * st;
+        el_s[c * 256 + i] += el_s[c * 256 + i + st];
+      }
+    }
+    __syncthreads();
+    if (tid < d) rec[1 + tid] = el_s[tid * 256];
+  } else {
+    const double e4 = block_sum(el, red);
+    if (tid == 0) rec[1] = e4;
+  }
+  if (tid == 0) {
+    rec[0] = e0;
+    rec[1 + L] = e1;
+    rec[2 + L] = e2s;
+    rec[3 + L] = e3;
+  }
+}
+
+template <bool ARD>
+__global__ void __launch_bounds__(256) k_batch_pass2(BatchArgs a) {
+  __shared__ __attribute__((aligned(16))) double xu_s[SGP_MAXD * MM], pp_s[MM * MM];
+  __shared__ double vec_s[3 * MM + SGP_MAXD], xs[SGP_MAXD * 64], red[256];
+  __shared__ double el_s[ARD ? SGP_MAXD * 256 : 1];
+  const int seg = blockIdx.x;
+  const int prob = a.seg_prob[seg];
+  const double* P = a.par + (int64_t)prob * a.pst;
+  if (P[BP_ACTIVE] == 0.0) return;
+  if (a.out[(int64_t)prob * BATCH_OUT + 1] != 0.0) return;   // the problem failed in k_batch_mm
+  const double* pm = a.pm + (int64_t)prob * BATCH_PM;
+  const int64_t row0 = a.seg_row0[seg];
+  const int rows = a.seg_rows[seg];
+  double* rec = a.rec2 + (int64_t)seg * BATCH_REC2;
+  switch (((int)P[BP_M] + 15) >> 4) {
+    case 1: pass2_body<1, ARD>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, red, el_s); break;
+    case 2: pass2_body<2, ARD>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, red, el_s); break;
+    case 3: pass2_body<3, ARD>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, red, el_s); break;
+    default: pass2_body<4, ARD>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, red, el_s); break;
+  }
+}
+
+// ------------------------------------------------------------------------------ finish
+// delbo_dcov_par (vi_functions.R:259-419) in adjoint form, as sgp_vi_finish composes it
+__global__ void __launch_bounds__(64) k_batch_finish(BatchArgs a) {
+  __shared__ double r2[SGP_MAXD + 4];
+  const int prob = blockIdx.x, tid = threadIdx.x;
+  const double* P = a.par + (int64_t)prob * a.pst;
+  if (P[BP_ACTIVE] == 0.0) return;
+  double* out = a.out + (int64_t)prob * BATCH_OUT;
+  if (out[1] != 0.0) return;
+  const int L = a.ard ? a.d : 1;
+  const int seg0 = (int)P[BP_SEG0], nseg = (int)P[BP_NSEG];
+  if (tid < L + 4) r2[tid] = rec_sum(a.rec2 + (int64_t)seg0 * BATCH_REC2 + tid, BATCH_REC2, nseg);
+  __syncthreads();
+  const double* sc = a.sc + (int64_t)prob * BATCH_SC;
+  const double sig2 = P[BP_SIG2], tau2 = P[BP_TAU2], z = P[BP_Z], delta = P[BP_DELTA];
+  const double n = P[BP_NROW];
+  if (tid == 0) out[2] = 2.0 * r2[0] + sc[BS_G22] - n * sig2 / tau2;
+  if (tid >= 1 && tid <= L) out[2 + tid] = r2[tid] + sc[BS_G22 + tid];
+  if (tid == L + 1) {
+    const double c_sum = r2[1 + L], c_cnt = r2[2 + L], c_dg = r2[3 + L];
+    const double trSinv = n / z - sc[BS_TRBS] / (z * z);
+    const double trW = 0.5 * (sc[BS_ATA] - trSinv);
+    out[2 + tid] = 2.0 * tau2 * (c_sum - (c_cnt - delta * c_dg) / tau2) + 2.0 * tau2 * trW -
+                   2.0 * sc[BS_TRACE];
+  }
+}
+
+// ------------------------------------------------------------------------------ posterior
+// vi_functions.R:1161-1180 as sgp_posterior_u evaluates it: u_mean - muu = K22 u,
+// u_var = K22 Bm^-1 K22, from the state the problem's last successful evaluation left
+__global__ void __launch_bounds__(256) k_batch_post(BatchArgs a, double* __restrict__ res) {
+  __shared__ __attribute__((aligned(16))) double A[MM * MM], Bm[MM * MM], T[MM * MM];
+  __shared__ double u_s[MM];
+  const int prob = blockIdx.x, tid = threadIdx.x;
+  const double* post = a.post + (int64_t)prob * a.post_stride;
+  const double* P = post + MM * MM + MM;
+  if (P[BP_ACTIVE] == 0.0) return;   // no successful evaluation yet (the state starts zeroed)
+  const int d = a.d, m = (int)P[BP_M];
+  const double sig2 = P[BP_SIG2], delta = P[BP_DELTA];
+  for (int e = tid; e < m * MM; e += 256) {
+    const int i = e >> 6, j = e & (MM - 1);
+    if (j >= m) continue;
+    A[i * MM + j] = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j)) + (i == j ? delta : 0.0);
+    Bm[i * MM + j] = post[i * MM + j];
+  }
+  if (tid < m) u_s[tid] = post[MM * MM + tid];
+  __syncthreads();
+  for (int e = tid; e < m * MM; e += 256) {
+    const int i = e >> 6, j = e & (MM - 1);
+    if (j >= m) continue;
+    double s = 0.0;
+    for (int k = 0; k < m; ++k) s = fma(A[i * MM + k], Bm[k * MM + j], s);
+    T[i * MM + j] = s;
+  }
+  __syncthreads();
+  double* r = res + (int64_t)prob * (MM * MM + MM);
+  for (int e = tid; e < m * MM; e += 256) {
+    const int i = e >> 6, j = e & (MM - 1);
+    if (j >= m) continue;
+    double s = 0.0;
+    for (int k = 0; k < m; ++k) s = fma(T[i * MM + k], A[k * MM + j], s);
+    r[i * MM + j] = s;
+  }
+  if (tid < m) {
+    double s = 0.0;
+    for (int k = 0; k < m; ++k) s = fma(A[tid * MM + k], u_s[k], s);
+    r[MM * MM + tid] = s;
+  }
+}
+
+}  // namespace
+
+hipError_t launch_batch_eval(const BatchArgs& a, hipStream_t s, hipEvent_t* ev) {
+  if (a.B < 1 || a.nseg < 1 || a.d < 1 || a.d > SGP_MAXD) return hipErrorInvalidValue;
+  hipError_t e = hipSuccess;
+  if (ev) e = hipEventRecord(ev[0], s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_batch_pass1, dim3((unsigned)a.nseg), dim3(256), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (ev && (e = hipEventRecord(ev[1], s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_batch_mm, dim3((unsigned)a.B), dim3(256), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (ev && (e = hipEventRecord(ev[2], s)) != hipSuccess) return e;
+  if (!a.obj_only) {
+    if (a.ard) hipLaunchKernelGGL(k_batch_pass2<true>, dim3((unsigned)a.nseg), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_batch_pass2<false>, dim3((unsigned)a.nseg), dim3(256), 0, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (ev && (e = hipEventRecord(ev[3], s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_batch_finish, dim3((unsigned)a.B), dim3(64), 0, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  } else if (ev && (e = hipEventRecord(ev[3], s)) != hipSuccess) {
+    return e;
+  }
+  if (ev) e = hipEventRecord(ev[4], s);
+  return e;
+}
+
+hipError_t launch_batch_post(const BatchArgs& a, double* res, hipStream_t s) {
+  if (a.B < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_batch_post, dim3((unsigned)a.B), dim3(256), 0, s, a, res);
+  return hipGetLastError();
+}

@@ -599,3 +599,43 @@ struct GatherSegs {
   int count;
 };
 hipError_t launch_rec_gather(const RecPass2& p2, const GatherSegs& g, double* dst, hipStream_t s);
+
+// ---------------------------------------------------------------- k_batch.hip
+// Batched small-knot VI (sgp_batch_eval_vi).
+#ifndef SGP_BATCH_MMAX
+#define SGP_BATCH_MMAX 64       // include/sgp.h
+#endif
+#ifndef SGP_BATCH_SEG_ROWS
+#define SGP_BATCH_SEG_ROWS 512  // include/sgp_diag.h: eight 64-row steps
+#endif
+// A problem's parameter block (doubles; integers are held exactly), stride 48 + 64 d
+enum {
+  BP_M = 0, BP_ACTIVE, BP_SIG2, BP_TAU2, BP_Z, BP_DELTA, BP_NROW, BP_RDET, BP_SEG0, BP_NSEG,
+  BP_RL = 16,                   // 1 / l_c, d values ("sqexp": 1 / l in each)
+  BP_U = 48                     // knots [c][64], zero beyond m
+};
+constexpr int BR_T = SGP_BATCH_MMAX * SGP_BATCH_MMAX, BR_RR = BR_T + SGP_BATCH_MMAX;
+constexpr int BATCH_REC1 = BR_RR + 8;    // pass 1's record: S (row stride 64) | t | r^T r
+constexpr int BATCH_REC2 = SGP_MAXD + 8; // pass 2's: sum W | the L length-scale sums | c_sum, c_cnt, c_dg
+constexpr int BPM_U = BR_T, BPM_KD = BPM_U + SGP_BATCH_MMAX;
+constexpr int BATCH_PM = BPM_KD + SGP_BATCH_MMAX;   // P' (row stride 64) | u | diag K22^-1
+enum { BS_TRACE = 0, BS_TRBS, BS_ATA, BS_G22 = 4 }; // the m x m stage's scalars; G22 terms: P values
+constexpr int BATCH_SC = BS_G22 + SGP_MAXD + 4;
+constexpr int BATCH_OUT = SGP_MAXD + 8;  // obj | status | grad (P values)
+struct BatchArgs {
+  const double *X, *y, *mu;     // the resident rows (X column-major, ld ldx)
+  int64_t ldx;
+  const double* par;            // B parameter blocks, stride pst
+  int pst, d, ard, obj_only;
+  int B, nseg;
+  const int* seg_prob;          // per segment: its problem, its first row, its rows
+  const int64_t* seg_row0;
+  const int* seg_rows;
+  double *rec1, *rec2, *pm, *sc, *out;
+  double* post;                 // per problem: Bm^-1 (row stride 64) | u | the parameter block
+  int post_stride;
+};
+// ev (or nullptr): 5 events recorded before pass 1, the m x m stage, pass 2, the finish and after
+hipError_t launch_batch_eval(const BatchArgs& a, hipStream_t s, hipEvent_t* ev);
+// res: per problem 64 * 64 + 64 doubles, u_var (row stride 64) | u_mean - muu
+hipError_t launch_batch_post(const BatchArgs& a, double* res, hipStream_t s);
