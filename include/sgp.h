@@ -481,6 +481,44 @@ int sgp_batch_eval_vi(sgp_batch* b, int kernel, const double* theta, int64_t ldt
                       int* status);
 int sgp_batch_posterior_u(sgp_batch* b, const double* muu, double* u_mean, double* u_var);
 
+/* Held-out prediction and scoring for a batch: predict_vi
+ * (R/vi_functions.R:1222-1336) and my_nlp(family = "gaussian") (R/evaluation_functions.R:14-20,
+ * with quirk Q23: pred_var + tau^2 as written) for every problem of the batch in three launches,
+ * from the state each problem's last successful evaluation left on the device -- what
+ * sgp_batch_posterior_u reads; a later evaluation of the problem that was not positive definite
+ * does not disturb it.  With u = Bm^-1 t / z of that evaluation, u_mean - muu = K22 u and
+ * u_var = K22 Bm^-1 K22, so muu cancels and, with k_i = k(x_i, U) without a nugget,
+ *   pred_mean_i = mu_i + k_i^T u
+ *   pred_var_i  = (tau^2 + sigma^2) + delta + k_i^T (Bm^-1 - K22^-1) k_i
+ *   nlp_i       = -dnorm(y_i, pred_mean_i, sqrt(pred_var_i + tau^2), log = TRUE)
+ * with the problem's own theta, knots, m and delta.
+ *
+ * set_test: Xt (ntest x d column-major, ld ldxt), yt (ntest values, or NULL: predict only) and
+ * mut (ntest values) are uploaded once; problem b's test rows are [trow0[b], trow0[b] + tnrow[b]).
+ * Ranges may overlap or coincide; tnrow[b] = 0 is allowed (nothing is written for b).  The call
+ * may be repeated and then replaces the test rows; sgp_batch_set_data leaves them alone.  All
+ * device and pinned memory sgp_batch_predict needs is allocated here: predict allocates nothing.
+ *
+ * predict: outputs are packed per problem in problem order: problem b's rows start at
+ * toff[b] = sum of tnrow[b'] over all b' < b (active or not), so pred_mean, pred_var and nlp hold
+ * sum tnrow values; problem b's stats are stats[4 b .. 4 b + 3] = {sum of the finite nlp, their
+ * count, the count of NaN rows, sum (pred_mean - y)^2}, as sgp_nlp defines them.  nlp and stats
+ * are both given or both NULL (no scoring).  active (B bytes, NULL = all): where active[b] == 0
+ * nothing of problem b is computed or written.  A non-finite mut entry is data: that row's mean is
+ * not finite, its nlp is NaN and it counts in stats[2] (sgp_nlp's rule).
+ * SGP_EINVAL before the first device call (sgp_diag_batch_test_args, sgp_diag.h, is the same
+ * check) for: a NULL handle or required pointer, ntest < 1, ldxt < ntest, tnrow[b] < 0, a range
+ * leaving [0, ntest), a non-finite Xt or yt, predict before set_test, nlp with yt = NULL, exactly
+ * one of nlp / stats NULL, and an active problem without a posterior (the first is named).
+ * Every sum has a fixed order and no problem reads another's data: a problem's outputs do not
+ * depend on B, its position, the other problems, `active` or the repeat -- bit for bit. */
+int sgp_batch_set_test(sgp_batch* b, const double* Xt, int64_t ntest, int64_t ldxt,
+                       const double* yt /* NULL: predict only */, const double* mut,
+                       const int64_t* trow0, const int64_t* tnrow);
+int sgp_batch_predict(sgp_batch* b, const unsigned char* active, double* pred_mean,
+                      double* pred_var, double* nlp /* NULL: no scoring */,
+                      double* stats /* 4 x B, NULL iff nlp is NULL */);
+
 /* Joint predictive scoring and draws from a Gaussian process: the branches of
  * the reference that use a full covariance -- my_nlp(mv = TRUE), my_nlp(family = "bernoulli",
  * mc = TRUE), my_kl(mv = TRUE) (R/evaluation_functions.R:21-26, 53-80, 120-133, 153-164) -- and the

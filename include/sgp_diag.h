@@ -152,6 +152,31 @@ int sgp_diag_batch_plan(const int64_t* row0, const int64_t* nrow, int64_t B, int
 struct sgp_batch;
 int sgp_diag_batch_timing(struct sgp_batch* b, int enable, double* stage_ms);
 
+/* Host only: the argument checks of sgp_batch_set_test (stage 0: d, B and the arguments Xt ..
+ * tnrow) and of sgp_batch_predict (stage 1: B and the arguments from have_test on) -- the very
+ * function both run before their first device call.  have_test / have_yt: whether set_test was
+ * called, and with a yt; has_state (B bytes): which problems have a posterior.  SGP_OK or
+ * SGP_EINVAL with sgp_last_error(). */
+int sgp_diag_batch_test_args(int stage, int d, int64_t B, const double* Xt, int64_t ntest,
+                             int64_t ldxt, const double* yt, const double* mut,
+                             const int64_t* trow0, const int64_t* tnrow, int have_test,
+                             int have_yt, const unsigned char* has_state,
+                             const unsigned char* active, const double* pred_mean,
+                             const double* pred_var, const double* nlp, const double* stats);
+
+/* Host only: the test-segment plan of sgp_batch_set_test: sgp_diag_batch_plan's rule applied to
+ * (trow0, tnrow), where tnrow[b] = 0 is allowed and yields no segment; seg_row0 is a row of Xt.
+ * toff (B + 1 values, or NULL): the problems' first rows in the packed outputs, toff[B] = sum
+ * tnrow. */
+int sgp_diag_batch_test_plan(const int64_t* trow0, const int64_t* tnrow, int64_t B, int64_t cap,
+                             int64_t* nseg, int64_t* seg_prob, int64_t* seg_row0,
+                             int64_t* seg_rows, int64_t* toff);
+
+/* stage_ms (3 doubles, or NULL): the times by HIP events of the m x m stage, the row pass and the
+ * finish of the batch's last sgp_batch_predict (zeros when they were not recorded); enable != 0
+ * records them from the next call on. */
+int sgp_diag_batch_predict_timing(struct sgp_batch* b, int enable, double* stage_ms);
+
 #ifdef __cplusplus
 }
 #endif

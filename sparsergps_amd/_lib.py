@@ -161,6 +161,18 @@ PROTOTYPES = {
     "sgp_diag_batch_plan": (C.c_int, [c_int64_p, c_int64_p, C.c_int64, C.c_int64, c_int64_p,
                                       c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
     "sgp_diag_batch_timing": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    # held-out prediction and scoring for a batch (Xt, ntest, ldxt, yt, mut, trow0, tnrow)
+    "sgp_batch_set_test": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, c_double_p,
+                                     c_double_p, c_int64_p, c_int64_p]),
+    "sgp_batch_predict": (C.c_int, [C.c_void_p, c_ubyte_p, c_double_p, c_double_p, c_double_p,
+                                    c_double_p]),
+    "sgp_diag_batch_test_args": (C.c_int, [C.c_int, C.c_int, C.c_int64, c_double_p, C.c_int64,
+                                           C.c_int64, c_double_p, c_double_p, c_int64_p,
+                                           c_int64_p, C.c_int, C.c_int, c_ubyte_p, c_ubyte_p,
+                                           c_double_p, c_double_p, c_double_p, c_double_p]),
+    "sgp_diag_batch_test_plan": (C.c_int, [c_int64_p, c_int64_p, C.c_int64, C.c_int64, c_int64_p,
+                                           c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
+    "sgp_diag_batch_predict_timing": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
     "sgp_sample_mvn": (C.c_int, [C.c_int, c_double_p, c_double_p, C.c_int64, C.c_int64, C.c_int64,
                                  C.c_uint64, c_double_p, C.c_int64]),
     "sgp_joint_nlp": (C.c_int, [C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, C.c_int64,

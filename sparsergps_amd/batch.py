@@ -6,6 +6,12 @@
                                one batch evaluation per iteration
   optimize_gp_batch            optimize_gp(family = "gaussian", sparse = TRUE, vi = TRUE,
                                xu_opt = "fixed") for a list of problems
+  SparseGPBatch.set_test / predict / score
+                               predict_vi (R/vi_functions.R:1222-1336) and score_gp's figures for
+                               every problem's held-out rows, from the posteriors the batch holds
+                               on the device
+  cross_validate_gp            k-fold cross-validation: the folds fitted in lockstep and scored on
+                               one batch
 
 Per problem the semantics are the single fit's (drivers._ascent with the knots fixed); a problem
 that meets its stop rule is retired through the evaluation's `active` mask while the others go
@@ -186,6 +192,128 @@ class SparseGPBatch:
         _lib.check(self._lib.sgp_diag_batch_timing(self._h, int(bool(enable)), _lib.dptr(out)))
         return out
 
+    # ------------------------------------------------------------------ held-out prediction
+    def set_test(self, x_test, y_test=None, mu_test=None, row0=None, nrow=None):
+        """The held-out rows (sgp_batch_set_test): x_test (nt x d), y_test (nt, or None: predict
+        only), mu_test (nt values, a scalar, or None for zeros: score_gp's rule for mu_pred);
+        problem b's test rows are [row0[b], row0[b] + nrow[b]) (None: all rows for every
+        problem).  Ranges may overlap; nrow[b] = 0 is allowed.  A repeated call replaces them."""
+        self._need()
+        X = np.asarray(x_test, dtype=np.float64)
+        X = np.asfortranarray(X.reshape(-1, self.d) if X.ndim != 2 else X)
+        nt = X.shape[0]
+        if X.shape[1] != self.d:
+            raise ValueError(f"set_test: x_test has {X.shape[1]} columns, the batch {self.d}")
+        yt = None if y_test is None else \
+            np.ascontiguousarray(np.asarray(y_test, dtype=np.float64).reshape(-1))
+        if yt is not None and yt.size != nt:
+            raise ValueError(f"set_test: {yt.size} y_test values for {nt} rows")
+        mut = np.zeros(nt) if mu_test is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(mu_test, dtype=np.float64), (nt,)))
+        if row0 is None and nrow is None:
+            row0, nrow = [0] * self.B, [nt] * self.B
+        r0 = np.ascontiguousarray(np.asarray(row0, dtype=np.int64).reshape(-1))
+        nr = np.ascontiguousarray(np.asarray(nrow, dtype=np.int64).reshape(-1))
+        if r0.size != self.B or nr.size != self.B:
+            raise ValueError(f"set_test: row0 and nrow must have one entry per problem ({self.B})")
+        i64 = lambda a: a.ctypes.data_as(_lib.c_int64_p)   # noqa: E731
+        _lib.check(self._lib.sgp_batch_set_test(
+            self._h, _lib.dptr(X), nt, nt, None if yt is None else _lib.dptr(yt), _lib.dptr(mut),
+            i64(r0), i64(nr)))
+        self._test = (r0, nr, np.concatenate([[0], np.cumsum(nr)]).astype(np.int64), yt)
+
+    def set_test_problems(self, tests):
+        """tests: [(x_b, y_b, mu_b), ...], one per problem (y_b None in all of them: predict only;
+        mu_b None: zeros), concatenated as from_problems concatenates the training rows."""
+        if len(tests) != self.B:
+            raise ValueError(f"set_test_problems: {len(tests)} test sets for {self.B} problems")
+        xs, ys, mus, row0, nrow = [], [], [], [], []
+        at = 0
+        for t in tests:
+            x = np.asarray(t[0], dtype=np.float64)
+            x = x.reshape(-1, self.d) if x.ndim != 2 else x
+            y = t[1] if len(t) > 1 else None
+            mu = t[2] if len(t) > 2 else None
+            xs.append(x)
+            ys.append(None if y is None else np.asarray(y, dtype=np.float64).reshape(-1))
+            mus.append(np.broadcast_to(np.asarray(0.0 if mu is None else mu, dtype=np.float64),
+                                       (x.shape[0],)))
+            row0.append(at)
+            nrow.append(x.shape[0])
+            at += x.shape[0]
+        if any(y is None for y in ys) and not all(y is None for y in ys):
+            raise ValueError("set_test_problems: y is given for some problems and not for others")
+        self.set_test(np.vstack(xs), None if ys[0] is None else np.concatenate(ys),
+                      np.concatenate(mus), row0, nrow)
+
+    def predict_raw(self, active, pred_mean, pred_var, nlp=None, stats=None):
+        """sgp_batch_predict on caller-owned arrays: pred_mean, pred_var (and nlp) of sum nrow
+        values, packed per problem in problem order, stats (B x 4); nlp and stats both or
+        neither.  Slots of inactive problems are left as they are."""
+        self._need()
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
+        _lib.check(self._lib.sgp_batch_predict(
+            self._h, None if act is None else act.ctypes.data_as(_lib.c_ubyte_p),
+            _lib.dptr(pred_mean), _lib.dptr(pred_var), None if nlp is None else _lib.dptr(nlp),
+            None if stats is None else _lib.dptr(stats)))
+
+    def _run_predict(self, active, score):
+        self._need()
+        test = getattr(self, "_test", None)
+        tot = int(test[2][-1]) if test else 0
+        pm, pv = np.full(tot + 1, np.nan), np.full(tot + 1, np.nan)
+        nlp = np.full(tot + 1, np.nan) if score else None
+        stats = np.zeros((self.B, 4)) if score else None
+        self.predict_raw(active, pm, pv, nlp, stats)
+        return test, pm, pv, nlp, stats
+
+    def predict(self, active=None):
+        """predict_vi for every active problem on its test rows, from the posterior of its last
+        successful evaluation: a list of {"pred_mean": (n_b, 1), "pred_var": (n_b,)}, None for
+        inactive problems."""
+        (_, nr, off, _), pm, pv, _, _ = self._run_predict(active, False)
+        return [None if active is not None and not active[b] else
+                {"pred_mean": pm[off[b]:off[b] + nr[b]].reshape(-1, 1).copy(),
+                 "pred_var": pv[off[b]:off[b] + nr[b]].copy()} for b in range(self.B)]
+
+    def score(self, active=None):
+        """score_gp(vi = True) for every active problem on its test rows: a list of {"pred",
+        "nlp", "median_nlp", "mean_nlp", "rmse", "srmse", "n_nan"} dicts (None for inactive
+        problems), the nlp with each problem's own tau."""
+        self._need()
+        test = getattr(self, "_test", None)
+        if test is not None and test[3] is None:
+            raise ValueError("SparseGPBatch.score: set_test was given no y_test")
+        (r0, nr, off, yt), pm, pv, nlp, stats = self._run_predict(active, True)
+        out = []
+        for b in range(self.B):
+            if active is not None and not active[b]:
+                out.append(None)
+                continue
+            n, o = int(nr[b]), int(off[b])
+            st = stats[b] if n else np.zeros(4)
+            y = yt[r0[b]:r0[b] + n]
+            v = nlp[o:o + n].copy()
+            rmse = float(np.sqrt(st[3] / n)) if n else float("nan")
+            sd = float(np.std(y, ddof=1)) if n > 1 else float("nan")
+            fin = v[np.isfinite(v)]
+            out.append({"pred": {"pred_mean": pm[o:o + n].reshape(-1, 1).copy(),
+                                 "pred_var": pv[o:o + n].copy()},
+                        "nlp": v,
+                        "median_nlp": float(np.median(fin)) if fin.size else float("nan"),
+                        "mean_nlp": float(st[0] / st[1]) if st[1] > 0 else float("nan"),
+                        "rmse": rmse, "srmse": rmse / sd, "n_nan": int(st[2])})
+        return out
+
+    def predict_stage_ms(self, enable=True):
+        """HIP-event times (ms) of the last predict / score's three stages (the m x m stage, the
+        row pass, the finish); records from the next call on."""
+        self._need()
+        out = np.zeros(3)
+        _lib.check(self._lib.sgp_diag_batch_predict_timing(self._h, int(bool(enable)),
+                                                           _lib.dptr(out)))
+        return out
+
     # ------------------------------------------------------------------ lifetime
     def _need(self):
         if not self._h:
@@ -326,6 +454,29 @@ def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o):
     return out
 
 
+def _per_problem(B, cov_par_start, xu, muu, who, unit):
+    """cov_par_start, xu and muu as B-lists: each is one value for all or a list with one per
+    problem (a list of numbers is one knot set / one muu)."""
+    per = lambda v, one: list(v) if isinstance(v, (list, tuple)) and not one(v) else [v] * B  # noqa: E731
+    starts = per(cov_par_start, lambda v: False)
+    is_arr = lambda v: len(v) > 0 and np.ndim(v[0]) == 0   # noqa: E731
+    xus = [xu] * B if isinstance(xu, np.ndarray) else per(xu, is_arr)
+    muus = [muu] * B if muu is None or isinstance(muu, np.ndarray) else per(muu, is_arr)
+    if len(starts) != B or len(xus) != B or len(muus) != B:
+        raise ValueError(f"{who}: cov_par_start, xu and muu must be one value or one "
+                         f"per {unit}")
+    return starts, xus, muus
+
+
+def _knots_and_muu(xu, muu):
+    """(m x d knots, muu): a muu that is None or not of m values is zeros."""
+    u = np.asarray(xu, dtype=np.float64)
+    u = u.reshape(-1, 1) if u.ndim == 1 else u
+    if muu is None or np.size(muu) != u.shape[0]:
+        muu = np.zeros(u.shape[0])
+    return u, np.asarray(muu, dtype=np.float64).reshape(-1)
+
+
 def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None):
     """optimize_gp(y, xy, cov_fun, cov_par_start, mu, family = "gaussian", sparse = TRUE,
     xu_opt = "fixed", xu, muu, vi = TRUE, opt) for each (xy, y, mu) of `problems`, fitted in
@@ -342,14 +493,7 @@ def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None):
         return [ERR_GA] * B
     if cov_fun not in ("sqexp", "ard"):
         return [ERR_COV] * B
-    per = lambda v, one: list(v) if isinstance(v, (list, tuple)) and not one(v) else [v] * B  # noqa: E731
-    starts = per(cov_par_start, lambda v: False)
-    is_arr = lambda v: len(v) > 0 and np.ndim(v[0]) == 0   # noqa: E731
-    xus = [xu] * B if isinstance(xu, np.ndarray) else per(xu, is_arr)
-    muus = [muu] * B if muu is None or isinstance(muu, np.ndarray) else per(muu, is_arr)
-    if len(starts) != B or len(xus) != B or len(muus) != B:
-        raise ValueError("optimize_gp_batch: cov_par_start, xu and muu must be one value or one "
-                         "per problem")
+    starts, xus, muus = _per_problem(B, cov_par_start, xu, muu, "optimize_gp_batch", "problem")
     out, keep = [None] * B, []
     for b, prob in enumerate(problems):
         n = np.asarray(prob[1]).size
@@ -357,13 +501,8 @@ def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None):
             out[b] = ERR_MAXKNOT
             continue
         xy = _mat(prob[0], n)
-        u = np.asarray(xus[b], dtype=np.float64)
-        u = u.reshape(-1, 1) if u.ndim == 1 else u
-        mb = muus[b]
-        if mb is None or np.size(mb) != u.shape[0]:
-            mb = np.zeros(u.shape[0])
-        keep.append((b, (xy, prob[1], prob[2] if len(prob) > 2 else None), u,
-                     np.asarray(mb, dtype=np.float64).reshape(-1)))
+        u, mb = _knots_and_muu(xus[b], muus[b])
+        keep.append((b, (xy, prob[1], prob[2] if len(prob) > 2 else None), u, mb))
     if keep:
         res = norm_grad_ascent_vi_batch([starts[b] for b, *_ in keep], cov_fun,
                                         [u for _, _, u, _ in keep], [p for _, p, _, _ in keep],
@@ -372,3 +511,92 @@ def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None):
             out[b] = {"results": r, "sparse": True, "family": "gaussian", "delta": o["delta"],
                       "xu_init": u}
     return out
+
+
+def cross_validate_gp(y, xy, cov_fun, cov_par_start, xu, folds=5, mu=None, muu=None, opt=None,
+                      rng=None):
+    """k-fold cross-validation of optimize_gp(family = "gaussian", sparse = TRUE, vi = TRUE,
+    xu_opt = "fixed"): every fold's fit runs in lockstep on one batch and every fold's held-out
+    rows are scored on it (SparseGPBatch.score), without the posteriors leaving the device.
+
+    folds: an integer (a random partition from rng, default np.random.default_rng(0)) or an
+    integer array of fold ids, one per row.  Fold f trains on the rows of every other fold and
+    holds its own out.  mu = None takes each fold's training mean(y) for its training rows and
+    its held-out rows; an array mu is split by rows.  cov_par_start, xu and muu: one value for
+    all folds or a list with one per fold.  The refusals are optimize_gp_batch's and come back as
+    its error string.
+
+    Returns {"folds": [{"model": an optimize_gp-shaped dict (predict_gp / score_gp take it),
+    "score": score_gp's dict for the held-out rows, or the fit's error, "test_rows": indices}],
+    "mean_nlp", "median_nlp" (over all held-out rows' finite nlp), "rmse" (over all held-out
+    rows), "fold_id"}; the pooled figures cover the folds that were scored."""
+    from .optimize import ERR_COV, ERR_GA, ERR_MAXKNOT, OPT_MASTER
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    n = y.size
+    xy = _mat(xy, n)
+    o = {k: (dict(v) if isinstance(v, dict) else v) for k, v in OPT_MASTER.items()}
+    for k, v in (opt or {}).items():
+        if k in o:
+            o[k] = dict(v) if isinstance(v, dict) else v
+    if o["optim_method"] == "ga":
+        return ERR_GA
+    if cov_fun not in ("sqexp", "ard"):
+        return ERR_COV
+    if np.ndim(folds) == 0:
+        k = int(folds)
+        if not 2 <= k <= n:
+            raise ValueError(f"cross_validate_gp: folds={k} outside [2, {n}]")
+        g = np.random.default_rng(0) if rng is None else rng
+        fold_id = np.empty(n, dtype=np.int64)
+        fold_id[g.permutation(n)] = np.arange(n) % k
+    else:
+        fold_id = np.asarray(folds, dtype=np.int64).reshape(-1)
+        if fold_id.size != n:
+            raise ValueError(f"cross_validate_gp: {fold_id.size} fold ids for {n} rows")
+    ids = np.unique(fold_id)
+    B = ids.size
+    if B < 2:
+        raise ValueError("cross_validate_gp: fewer than two folds")
+    test_rows = [np.flatnonzero(fold_id == f) for f in ids]
+    train_rows = [np.flatnonzero(fold_id != f) for f in ids]
+    if any(o["maxknot"] >= tr.size for tr in train_rows):
+        return ERR_MAXKNOT
+    starts, xus, muus = _per_problem(B, cov_par_start, xu, muu, "cross_validate_gp", "fold")
+    mu_all = None if mu is None else np.broadcast_to(np.asarray(mu, dtype=np.float64), (n,))
+    problems, tests, us, mbs = [], [], [], []
+    for b in range(B):
+        tr, te = train_rows[b], test_rows[b]
+        mu_tr = np.full(tr.size, y[tr].mean()) if mu_all is None else mu_all[tr]
+        mu_te = np.full(te.size, y[tr].mean()) if mu_all is None else mu_all[te]
+        problems.append((xy[tr], y[tr], mu_tr))
+        tests.append((xy[te], y[te], mu_te))
+        u, mb = _knots_and_muu(xus[b], muus[b])
+        us.append(u)
+        mbs.append(mb)
+    batch = SparseGPBatch.from_problems(problems)
+    try:
+        res = norm_grad_ascent_vi_batch(starts, cov_fun, us, batch, mbs, o)
+        ok = np.array(["error" not in r for r in res], dtype=np.uint8)
+        scores = [None] * B
+        if ok.any():
+            batch.set_test_problems(tests)
+            scores = batch.score(ok)
+    finally:
+        batch.close()
+    out, nlps, errs = [], [], []
+    for b in range(B):
+        model = {"results": res[b], "sparse": True, "family": "gaussian", "delta": o["delta"],
+                 "xu_init": us[b]}
+        out.append({"model": model, "score": scores[b] if ok[b] else res[b]["error"],
+                    "test_rows": test_rows[b]})
+        if ok[b]:
+            nlps.append(scores[b]["nlp"])
+            errs.append(scores[b]["pred"]["pred_mean"].reshape(-1) - tests[b][1])
+    nlp = np.concatenate(nlps) if nlps else np.zeros(0)
+    err = np.concatenate(errs) if errs else np.zeros(0)
+    fin = nlp[np.isfinite(nlp)]
+    return {"folds": out,
+            "mean_nlp": float(fin.mean()) if fin.size else float("nan"),
+            "median_nlp": float(np.median(fin)) if fin.size else float("nan"),
+            "rmse": float(np.sqrt(np.mean(err ** 2))) if err.size else float("nan"),
+            "fold_id": fold_id}

@@ -5262,6 +5262,18 @@ struct sgp_batch {
   int last_ard = 0;
   float stage_ms[4] = {0.f, 0.f, 0.f, 0.f};
   bool timing = false;
+  // the held-out rows (sgp_batch_set_test) and what sgp_batch_predict works in
+  bool have_test = false, have_yt = false, ptiming = false;
+  int64_t ntest = 0, ntseg = 0, ttot = 0;
+  std::vector<int64_t> tnrow, toff;
+  double *Xt = nullptr, *yt = nullptr, *mut = nullptr, *pw = nullptr, *prec = nullptr,
+         *pout = nullptr;            // pout: pred_mean | pred_var | nlp (ttot each) | stats (4 B)
+  int *act = nullptr, *tseg_prob = nullptr, *tseg_rows = nullptr, *tprob_seg = nullptr;
+  int64_t *tseg_row0 = nullptr, *tseg_out = nullptr;
+  double* h_pout = nullptr;          // pinned
+  int* h_act = nullptr;              // pinned
+  hipEvent_t pev[4] = {nullptr, nullptr, nullptr, nullptr};
+  float pstage_ms[3] = {0.f, 0.f, 0.f};
 };
 
 namespace {
@@ -5355,9 +5367,126 @@ int batch_check_eval(int d, int64_t B, int kernel, const double* theta, int64_t 
   return SGP_OK;
 }
 
+// The test-row plan: problem p's tnrow[p] test rows in segments of at most SGP_BATCH_SEG_ROWS
+// counted from its own first test row (sgp_diag_batch_plan's rule; a problem without rows has no
+// segment), and toff, the problems' first rows in the packed outputs.
+int64_t batch_test_plan(const int64_t* trow0, const int64_t* tnrow, int64_t B, int64_t cap,
+                        int64_t* seg_prob, int64_t* seg_row0, int64_t* seg_rows, int64_t* toff) {
+  int64_t k = 0, at = 0;
+  for (int64_t p = 0; p < B; ++p) {
+    if (toff) toff[p] = at;
+    for (int64_t r = 0; r < tnrow[p]; r += SGP_BATCH_SEG_ROWS, ++k)
+      if (k < cap) {
+        seg_prob[k] = p;
+        seg_row0[k] = trow0[p] + r;
+        seg_rows[k] = std::min<int64_t>(SGP_BATCH_SEG_ROWS, tnrow[p] - r);
+      }
+    at += tnrow[p];
+  }
+  if (toff) toff[B] = at;
+  return k;
+}
+
+// The argument checks of sgp_batch_set_test (stage 0) and sgp_batch_predict (stage 1), made
+// before the first device call; sgp_diag_batch_test_args is this function.
+int batch_check_test(int stage, int d, int64_t B, const double* Xt, int64_t ntest, int64_t ldxt,
+                     const double* yt, const double* mut, const int64_t* trow0,
+                     const int64_t* tnrow, int have_test, int have_yt,
+                     const unsigned char* has_state, const unsigned char* active,
+                     const double* pred_mean, const double* pred_var, const double* nlp,
+                     const double* stats) {
+  if (B < 1 || B > INT32_MAX) { set_err("sgp_batch: B=%lld < 1", (long long)B); return SGP_EINVAL; }
+  if (stage == 0) {
+    if (!Xt || !mut || !trow0 || !tnrow) {
+      set_err("sgp_batch_set_test: Xt, mut, trow0 and tnrow must not be NULL");
+      return SGP_EINVAL;
+    }
+    if (d < 1 || d > SGP_MAXD) {
+      set_err("input dimension d=%d outside [1, %d]", d, SGP_MAXD);
+      return SGP_EINVAL;
+    }
+    if (ntest < 1 || ldxt < ntest) {
+      set_err("sgp_batch_set_test: ntest=%lld, ldxt=%lld (need ntest >= 1 and ldxt >= ntest)",
+              (long long)ntest, (long long)ldxt);
+      return SGP_EINVAL;
+    }
+    int64_t segs = 0, tot = 0;
+    for (int64_t b = 0; b < B; ++b) {
+      if (tnrow[b] < 0) {
+        set_err("sgp_batch_set_test: problem %lld has tnrow=%lld < 0", (long long)b,
+                (long long)tnrow[b]);
+        return SGP_EINVAL;
+      }
+      if (trow0[b] < 0 || trow0[b] > ntest - tnrow[b]) {
+        set_err("sgp_batch_set_test: problem %lld's test rows [%lld, %lld) leave [0, %lld)",
+                (long long)b, (long long)trow0[b], (long long)(trow0[b] + tnrow[b]),
+                (long long)ntest);
+        return SGP_EINVAL;
+      }
+      segs += (tnrow[b] + SGP_BATCH_SEG_ROWS - 1) / SGP_BATCH_SEG_ROWS;
+      tot += tnrow[b];
+      if (segs > INT32_MAX / 2 || tot > (int64_t)1 << 40) {
+        set_err("sgp_batch_set_test: too many test rows");
+        return SGP_EINVAL;
+      }
+    }
+    int64_t bad = 0;
+    for (int c = 0; c < d; ++c)
+      if (!finite_all(Xt + (int64_t)c * ldxt, ntest, &bad)) {
+        set_err("sgp_batch_set_test: Xt[%lld, %d] is not finite", (long long)bad, c);
+        return SGP_EINVAL;
+      }
+    if (yt && !finite_all(yt, ntest, &bad)) {
+      set_err("sgp_batch_set_test: yt[%lld] is not finite", (long long)bad);
+      return SGP_EINVAL;
+    }
+    return SGP_OK;
+  }
+  if (stage != 1) { set_err("sgp_diag_batch_test_args: stage=%d", stage); return SGP_EINVAL; }
+  if (!pred_mean || !pred_var) {
+    set_err("sgp_batch_predict: pred_mean and pred_var must not be NULL");
+    return SGP_EINVAL;
+  }
+  if ((nlp == nullptr) != (stats == nullptr)) {
+    set_err("sgp_batch_predict: nlp and stats must both be given or both be NULL");
+    return SGP_EINVAL;
+  }
+  if (!have_test) {
+    set_err("sgp_batch_predict: no test rows (call sgp_batch_set_test first)");
+    return SGP_EINVAL;
+  }
+  if (nlp && !have_yt) {
+    set_err("sgp_batch_predict: nlp asked for, but sgp_batch_set_test had yt = NULL");
+    return SGP_EINVAL;
+  }
+  if (!has_state) { set_err("sgp_batch_predict: has_state is NULL"); return SGP_EINVAL; }
+  for (int64_t b = 0; b < B; ++b)
+    if ((!active || active[b]) && !has_state[b]) {
+      set_err("sgp_batch_predict: problem %lld has no posterior (no successful evaluation since "
+              "create / set_data)", (long long)b);
+      return SGP_EINVAL;
+    }
+  return SGP_OK;
+}
+
+void batch_free_test(sgp_batch* b) {
+  for (double** p : {&b->Xt, &b->yt, &b->mut, &b->pw, &b->prec, &b->pout})
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+  for (int** p : {&b->act, &b->tseg_prob, &b->tseg_rows, &b->tprob_seg})
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+  for (int64_t** p : {&b->tseg_row0, &b->tseg_out})
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+  if (b->h_pout) { (void)hipHostFree(b->h_pout); b->h_pout = nullptr; }
+  if (b->h_act) { (void)hipHostFree(b->h_act); b->h_act = nullptr; }
+  b->have_test = b->have_yt = false;
+}
+
 void batch_free(sgp_batch* b) {
   (void)hipSetDevice(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
+  batch_free_test(b);
+  for (hipEvent_t e : b->pev)
+    if (e) (void)hipEventDestroy(e);
   for (double* p : {b->X, b->y, b->mu, b->par, b->rec1, b->rec2, b->pm, b->sc, b->out, b->post,
                     b->res})
     if (p) (void)hipFree(p);
@@ -5647,6 +5776,163 @@ int sgp_diag_batch_timing(sgp_batch* b, int enable, double* stage_ms) {
   if (stage_ms)
     for (int q = 0; q < 4; ++q) stage_ms[q] = b->timing ? (double)b->stage_ms[q] : 0.0;
   b->timing = enable != 0;
+  return SGP_OK;
+}
+
+// ------------------------------------------------------------------------- batched prediction
+// sgp_batch_set_test / sgp_batch_predict (include/sgp.h)
+int sgp_diag_batch_test_args(int stage, int d, int64_t B, const double* Xt, int64_t ntest,
+                             int64_t ldxt, const double* yt, const double* mut,
+                             const int64_t* trow0, const int64_t* tnrow, int have_test,
+                             int have_yt, const unsigned char* has_state,
+                             const unsigned char* active, const double* pred_mean,
+                             const double* pred_var, const double* nlp, const double* stats) {
+  return batch_check_test(stage, d, B, Xt, ntest, ldxt, yt, mut, trow0, tnrow, have_test, have_yt,
+                          has_state, active, pred_mean, pred_var, nlp, stats);
+}
+
+int sgp_diag_batch_test_plan(const int64_t* trow0, const int64_t* tnrow, int64_t B, int64_t cap,
+                             int64_t* nseg, int64_t* seg_prob, int64_t* seg_row0,
+                             int64_t* seg_rows, int64_t* toff) {
+  if (!trow0 || !tnrow || B < 1 || !nseg || cap < 0 ||
+      (cap > 0 && (!seg_prob || !seg_row0 || !seg_rows))) {
+    set_err("invalid sgp_diag_batch_test_plan arguments");
+    return SGP_EINVAL;
+  }
+  for (int64_t p = 0; p < B; ++p)
+    if (tnrow[p] < 0 || trow0[p] < 0) {
+      set_err("sgp_diag_batch_test_plan: problem %lld has trow0=%lld, tnrow=%lld", (long long)p,
+              (long long)trow0[p], (long long)tnrow[p]);
+      return SGP_EINVAL;
+    }
+  *nseg = batch_test_plan(trow0, tnrow, B, cap, seg_prob, seg_row0, seg_rows, toff);
+  return SGP_OK;
+}
+
+int sgp_batch_set_test(sgp_batch* b, const double* Xt, int64_t ntest, int64_t ldxt,
+                       const double* yt, const double* mut, const int64_t* trow0,
+                       const int64_t* tnrow) {
+  if (!b) { set_err("sgp_batch_set_test: the sgp_batch is NULL"); return SGP_EINVAL; }
+  const int cst = batch_check_test(0, b->d, b->B, Xt, ntest, ldxt, yt, mut, trow0, tnrow, 0, 0,
+                                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (cst != SGP_OK) return cst;
+  const int64_t B = b->B;
+  const int d = b->d;
+  std::vector<int64_t> toff((size_t)B + 1);
+  const int64_t nseg = batch_test_plan(trow0, tnrow, B, 0, nullptr, nullptr, nullptr, toff.data());
+  std::vector<int64_t> sp((size_t)nseg + 1), s0((size_t)nseg + 1), sr((size_t)nseg + 1);
+  batch_test_plan(trow0, tnrow, B, nseg, sp.data(), s0.data(), sr.data(), nullptr);
+  std::vector<int> spi((size_t)nseg + 1), sri((size_t)nseg + 1), ps((size_t)(2 * B), 0);
+  std::vector<int64_t> so((size_t)nseg + 1);
+  for (int64_t k = 0; k < nseg; ++k) {
+    const int64_t p = sp[(size_t)k];
+    spi[(size_t)k] = (int)p;
+    sri[(size_t)k] = (int)sr[(size_t)k];
+    so[(size_t)k] = toff[(size_t)p] + (s0[(size_t)k] - trow0[p]);
+    if (ps[(size_t)(2 * p + 1)]++ == 0) ps[(size_t)(2 * p)] = (int)k;
+  }
+  const int64_t tot = toff[(size_t)B], nout = 3 * std::max<int64_t>(tot, 1) + 4 * B;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  batch_free_test(b);
+  for (hipEvent_t& e : b->pev)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  b->ntest = ntest;
+  b->ntseg = nseg;
+  b->ttot = tot;
+  b->tnrow.assign(tnrow, tnrow + B);
+  b->toff = toff;
+  HIPCHK(hipMalloc(&b->Xt, sizeof(double) * ntest * d));
+  HIPCHK(hipMalloc(&b->mut, sizeof(double) * ntest));
+  if (yt) HIPCHK(hipMalloc(&b->yt, sizeof(double) * ntest));
+  HIPCHK(hipMalloc(&b->pw, sizeof(double) * B * BATCH_PW));
+  HIPCHK(hipMalloc(&b->prec, sizeof(double) * (nseg + 1) * BATCH_PREC));
+  HIPCHK(hipMalloc(&b->pout, sizeof(double) * nout));
+  HIPCHK(hipMalloc(&b->act, sizeof(int) * B));
+  HIPCHK(hipMalloc(&b->tseg_prob, sizeof(int) * (nseg + 1)));
+  HIPCHK(hipMalloc(&b->tseg_rows, sizeof(int) * (nseg + 1)));
+  HIPCHK(hipMalloc(&b->tprob_seg, sizeof(int) * 2 * B));
+  HIPCHK(hipMalloc(&b->tseg_row0, sizeof(int64_t) * (nseg + 1)));
+  HIPCHK(hipMalloc(&b->tseg_out, sizeof(int64_t) * (nseg + 1)));
+  HIPCHK(hipHostMalloc(&b->h_pout, sizeof(double) * nout));
+  HIPCHK(hipHostMalloc(&b->h_act, sizeof(int) * B));
+  HIPCHK(hipMemsetAsync(b->pw, 0, sizeof(double) * B * BATCH_PW, b->stream));
+  HIPCHK(hipMemsetAsync(b->pout, 0, sizeof(double) * nout, b->stream));
+  HIPCHK(hipMemcpy2DAsync(b->Xt, sizeof(double) * ntest, Xt, sizeof(double) * ldxt,
+                          sizeof(double) * ntest, (size_t)d, hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->mut, mut, sizeof(double) * ntest, hipMemcpyHostToDevice, b->stream));
+  if (yt) HIPCHK(hipMemcpyAsync(b->yt, yt, sizeof(double) * ntest, hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->tseg_prob, spi.data(), sizeof(int) * (nseg + 1), hipMemcpyHostToDevice,
+                        b->stream));
+  HIPCHK(hipMemcpyAsync(b->tseg_rows, sri.data(), sizeof(int) * (nseg + 1), hipMemcpyHostToDevice,
+                        b->stream));
+  HIPCHK(hipMemcpyAsync(b->tprob_seg, ps.data(), sizeof(int) * 2 * B, hipMemcpyHostToDevice,
+                        b->stream));
+  HIPCHK(hipMemcpyAsync(b->tseg_row0, s0.data(), sizeof(int64_t) * (nseg + 1),
+                        hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(b->tseg_out, so.data(), sizeof(int64_t) * (nseg + 1),
+                        hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  b->have_test = true;
+  b->have_yt = yt != nullptr;
+  return SGP_OK;
+}
+
+int sgp_batch_predict(sgp_batch* b, const unsigned char* active, double* pred_mean,
+                      double* pred_var, double* nlp, double* stats) {
+  if (!b) { set_err("sgp_batch_predict: the sgp_batch is NULL"); return SGP_EINVAL; }
+  const int cst = batch_check_test(
+      1, b->d, b->B, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, b->have_test, b->have_yt,
+      reinterpret_cast<const unsigned char*>(b->has_state.data()), active, pred_mean, pred_var,
+      nlp, stats);
+  if (cst != SGP_OK) return cst;
+  const int64_t B = b->B, tot = b->ttot, cap = std::max<int64_t>(tot, 1);
+  bool any = false;
+  for (int64_t p = 0; p < B; ++p) {
+    b->h_act[p] = (!active || active[p]) ? 1 : 0;
+    any = any || b->h_act[p];
+  }
+  if (!any) return SGP_OK;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipMemcpyAsync(b->act, b->h_act, sizeof(int) * B, hipMemcpyHostToDevice, b->stream));
+  BatchPredArgs p;
+  p.Xt = b->Xt; p.yt = b->yt; p.mut = b->mut; p.ldxt = b->ntest;
+  p.act = b->act;
+  p.seg_prob = b->tseg_prob; p.seg_row0 = b->tseg_row0; p.seg_rows = b->tseg_rows;
+  p.seg_out = b->tseg_out; p.prob_seg = b->tprob_seg;
+  p.nseg = (int)b->ntseg; p.score = nlp ? 1 : 0;
+  p.pw = b->pw; p.rec = b->prec;
+  p.pm = b->pout; p.pv = b->pout + cap; p.nlp = b->pout + 2 * cap; p.stats = b->pout + 3 * cap;
+  HIPCHK(launch_batch_predict(batch_args(b, b->last_ard, 0), p, b->stream,
+                              b->ptiming ? b->pev : nullptr));
+  const int64_t ncopy = nlp ? 3 * cap + 4 * B : 2 * cap;
+  HIPCHK(hipMemcpyAsync(b->h_pout, b->pout, sizeof(double) * ncopy, hipMemcpyDeviceToHost,
+                        b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (b->ptiming)
+    for (int q = 0; q < 3; ++q)
+      HIPCHK(hipEventElapsedTime(&b->pstage_ms[q], b->pev[q], b->pev[q + 1]));
+  for (int64_t q = 0; q < B; ++q) {
+    if (!b->h_act[q]) continue;
+    const int64_t o = b->toff[(size_t)q], nr = b->tnrow[(size_t)q];
+    if (nr == 0) continue;   // no segment: nothing is written
+    std::copy(b->h_pout + o, b->h_pout + o + nr, pred_mean + o);
+    std::copy(b->h_pout + cap + o, b->h_pout + cap + o + nr, pred_var + o);
+    if (nlp) {
+      std::copy(b->h_pout + 2 * cap + o, b->h_pout + 2 * cap + o + nr, nlp + o);
+      std::copy(b->h_pout + 3 * cap + 4 * q, b->h_pout + 3 * cap + 4 * q + 4, stats + 4 * q);
+    }
+  }
+  return SGP_OK;
+}
+
+/* stage_ms (3 doubles, or NULL): HIP-event times of the m x m stage, the row pass and the finish
+ * of the last sgp_batch_predict; enable != 0 records them from the next call on. */
+int sgp_diag_batch_predict_timing(sgp_batch* b, int enable, double* stage_ms) {
+  if (!b) { set_err("sgp_diag_batch_predict_timing: the sgp_batch is NULL"); return SGP_EINVAL; }
+  if (stage_ms)
+    for (int q = 0; q < 3; ++q) stage_ms[q] = b->ptiming ? (double)b->pstage_ms[q] : 0.0;
+  b->ptiming = enable != 0;
   return SGP_OK;
 }
 

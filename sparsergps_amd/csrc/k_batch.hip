@@ -17,9 +17,13 @@
 // layout meets it again for W = G o K.  Every sum has a fixed order, no kernel uses atomics, and
 // nothing a problem computes reads another problem's data: results are bit-identical whatever
 // the batch, the position, `active` or the repeat.
+// Held-out prediction and scoring from that state (sgp_batch_predict), below
+// the evaluation's kernels: k_batch_pred_mm per problem, k_batch_predict per test segment,
+// k_batch_pred_finish per problem, under the same rules.
 #include <math.h>
 
 #include "sgp_internal.h"
+#include "sgp_quad.h"
 
 namespace {
 
@@ -607,6 +611,193 @@ __global__ void __launch_bounds__(256) k_batch_post(BatchArgs a, double* __restr
   }
 }
 
+// ------------------------------------------------------------------------------ prediction
+// sgp_batch_predict: predict_vi (R/vi_functions.R:1222-1336) on the state the
+// problem's last successful evaluation left in `post`.  With u_mean - muu = K22 u and u_var =
+// K22 Bm^-1 K22 the reference's Sigma22^-1 (u_mean - muu) is u and its Sigma22^-1 u_var Sigma22^-1
+// - Sigma22^-1 is T = Bm^-1 - K22^-1:
+//   pred_mean_i = mu_i + k_i^T u,   pred_var_i = (tau^2 + sigma^2) + delta + k_i^T T k_i
+// K22 is rebuilt as k_batch_mm built it and swept by the same code, so the sweep succeeds as it
+// did there.
+__global__ void __launch_bounds__(256) k_batch_pred_mm(BatchArgs a, BatchPredArgs p) {
+  __shared__ __attribute__((aligned(16))) double A[MM * MM];
+  __shared__ double ck[MM];
+  const int prob = blockIdx.x, tid = threadIdx.x;
+  if (!p.act[prob]) return;
+  const double* post = a.post + (int64_t)prob * a.post_stride;
+  const double* P = post + MM * MM + MM;
+  if (P[BP_ACTIVE] == 0.0) return;   // no successful evaluation (the host refuses this before)
+  const int d = a.d, m = (int)P[BP_M];
+  const double sig2 = P[BP_SIG2], tau2 = P[BP_TAU2], delta = P[BP_DELTA];
+  for (int e = tid; e < m * MM; e += 256) {
+    const int i = e >> 6, j = e & (MM - 1);
+    if (j >= m) continue;
+    A[i * MM + j] = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j)) + (i == j ? delta : 0.0);
+  }
+  double ld22 = 0.0;
+  const int st = sweep_spd(A, m, ck, &ld22);
+  double* w = p.pw + (int64_t)prob * BATCH_PW;
+  if (tid == 0) w[BPW_C0] = st ? NAN : (tau2 + sig2) + delta;
+  if (st) return;
+  for (int e = tid; e < m * MM; e += 256) {
+    const int i = e >> 6, j = e & (MM - 1);
+    if (j >= m) continue;
+    w[i * MM + j] = post[i * MM + j] - A[i * MM + j];
+  }
+}
+
+// One test segment: 64 rows per step in pass 2's layout (lane l on row l & 15 and knots
+// 4 s + (l >> 4)); Q = K T by MFMA with T the A operand from LDS, whose result layout meets k's
+// again at s = 4 cb + r, so k^T T k = sum_j Q_ij K_ij and k^T u are fma chains over s in the lane
+// and one xor-shuffle over the four lane groups.  sv: 4 x 64, the step's rows' stats terms; the
+// four sums go over the rows in row order (thread q < 4 owns sum q).
+template <int NT>
+__device__ __forceinline__ void predict_body(const BatchArgs& a, const BatchPredArgs& p,
+                                             const double* __restrict__ post,
+                                             const double* __restrict__ w, int64_t row0, int rows,
+                                             int64_t out0, double* __restrict__ rec, double* xu_s,
+                                             double* pp_s, double* vec_s, double* xs, double* sv) {
+  constexpr int Mp = 16 * NT, SN = 4 * NT;
+  const double* P = post + MM * MM + MM;
+  const int d = a.d, m = (int)P[BP_M];
+  const double sig2 = P[BP_SIG2], c0 = w[BPW_C0], tau = sqrt(P[BP_TAU2]);
+  double* u_s = vec_s;             // [g][s]
+  double* mus = vec_s + MM;        // 64: mu of this step's rows
+  double* ys = vec_s + 2 * MM;     // 64: y of this step's rows
+  double* rl_s = vec_s + 3 * MM;   // d
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, g = lane >> 4;
+  const bool score = p.score != 0;
+
+  for (int q = tid; q < d * Mp; q += 256) {
+    const int c = q / Mp, j = q - c * Mp;
+    xu_s[(c * 4 + (j & 3)) * SN + (j >> 2)] = P[BP_U + c * MM + j];
+  }
+  for (int q = tid; q < Mp * Mp; q += 256) {
+    const int i = q / Mp, j = q - i * Mp;
+    pp_s[q] = (i < m && j < m) ? w[i * MM + j] : 0.0;
+  }
+  for (int q = tid; q < Mp; q += 256) u_s[(q & 3) * SN + (q >> 2)] = q < m ? post[MM * MM + q] : 0.0;
+  for (int q = tid; q < d; q += 256) rl_s[q] = P[BP_RL + q];
+
+  double ssum = 0.0;   // thread q < 4: stats term q over the rows so far
+  for (int step = 0; step * 64 < rows; ++step) {
+    __syncthreads();   // the staging above / the previous step's reads of xs and writes of sv
+    for (int q = tid; q < d * 64; q += 256) {
+      const int c = q >> 6, i = q & 63;
+      const int row = step * 64 + i;
+      xs[q] = row < rows ? p.Xt[(int64_t)c * p.ldxt + row0 + row] : 0.0;
+    }
+    if (tid < 64) {
+      const int row = step * 64 + tid;
+      mus[tid] = row < rows ? p.mut[row0 + row] : 0.0;
+      ys[tid] = (score && row < rows) ? p.yt[row0 + row] : 0.0;
+    }
+    if (score && step > 0 && tid < 4)   // the previous step's 64 rows
+      for (int i = 0; i < 64; ++i) ssum += sv[tid * 64 + i];
+    __syncthreads();
+
+    const int row = step * 64 + wv * 16 + r16;
+    const bool iv = row < rows;
+    const double* xr = xs + wv * 16 + r16;
+    double e2[SN], kf[SN];
+#pragma unroll
+    for (int s = 0; s < SN; ++s) e2[s] = 0.0;
+    for (int c = 0; c < d; ++c) {
+      const double xc = xr[c * 64], rl = rl_s[c];
+      const double* u = xu_s + (c * 4 + g) * SN;
+#pragma unroll
+      for (int s = 0; s < SN; ++s) {
+        const double t = (xc - u[s]) * rl;   // the raw difference first: coincidence stays exact
+        e2[s] = fma(t, t, e2[s]);
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < SN; ++s) {
+      const double v = sig2 * sgp_exp_nonpos(-0.5 * e2[s]);
+      kf[s] = (iv && 4 * s + g < m) ? v : 0.0;
+    }
+    d4 acc[NT];
+#pragma unroll
+    for (int cb = 0; cb < NT; ++cb) acc[cb] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < SN; ++s)
+#pragma unroll
+      for (int cb = 0; cb < NT; ++cb)
+        acc[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(pp_s[(4 * s + g) * Mp + 16 * cb + r16],
+                                                       kf[s], acc[cb], 0, 0, 0);
+    double ku = 0.0, kq = 0.0;
+#pragma unroll
+    for (int cb = 0; cb < NT; ++cb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int s = 4 * cb + r;
+        ku = fma(kf[s], u_s[g * SN + s], ku);
+        kq = fma(acc[cb][r], kf[s], kq);
+      }
+    ku += __shfl_xor(ku, 16, 64);
+    ku += __shfl_xor(ku, 32, 64);
+    kq += __shfl_xor(kq, 16, 64);
+    kq += __shfl_xor(kq, 32, 64);
+    if (g == 0) {
+      const int i = wv * 16 + r16;
+      const double mean = mus[i] + ku, var = c0 + kq;
+      if (iv) {
+        p.pm[out0 + row] = mean;
+        p.pv[out0 + row] = var;
+      }
+      if (score) {
+        const double y = ys[i];
+        const double v = quad_nlp_gaussian(y, mean, var, tau);
+        if (iv) p.nlp[out0 + row] = v;
+        const bool fin = iv && fabs(v) <= 1.79769313486231570815e308;
+        const double e = mean - y;
+        sv[i] = fin ? v : 0.0;
+        sv[64 + i] = fin ? 1.0 : 0.0;
+        sv[128 + i] = (iv && v != v) ? 1.0 : 0.0;
+        sv[192 + i] = iv ? e * e : 0.0;
+      }
+    }
+  }
+  if (score) {
+    __syncthreads();
+    if (tid < 4) {
+      const int last = rows - ((rows - 1) >> 6) * 64;   // the rows of the last step
+      for (int i = 0; i < last; ++i) ssum += sv[tid * 64 + i];
+      rec[tid] = ssum;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_batch_predict(BatchArgs a, BatchPredArgs p) {
+  __shared__ __attribute__((aligned(16))) double xu_s[SGP_MAXD * MM], pp_s[MM * MM];
+  __shared__ double vec_s[3 * MM + SGP_MAXD], xs[SGP_MAXD * 64], sv[4 * 64];
+  const int seg = blockIdx.x;
+  const int prob = p.seg_prob[seg];
+  if (!p.act[prob]) return;
+  const double* post = a.post + (int64_t)prob * a.post_stride;
+  if (post[MM * MM + MM + BP_ACTIVE] == 0.0) return;
+  const double* w = p.pw + (int64_t)prob * BATCH_PW;
+  const int64_t row0 = p.seg_row0[seg], out0 = p.seg_out[seg];
+  const int rows = p.seg_rows[seg];
+  double* rec = p.rec + (int64_t)seg * BATCH_PREC;
+  switch (((int)post[MM * MM + MM + BP_M] + 15) >> 4) {
+    case 1: predict_body<1>(a, p, post, w, row0, rows, out0, rec, xu_s, pp_s, vec_s, xs, sv); break;
+    case 2: predict_body<2>(a, p, post, w, row0, rows, out0, rec, xu_s, pp_s, vec_s, xs, sv); break;
+    case 3: predict_body<3>(a, p, post, w, row0, rows, out0, rec, xu_s, pp_s, vec_s, xs, sv); break;
+    default: predict_body<4>(a, p, post, w, row0, rows, out0, rec, xu_s, pp_s, vec_s, xs, sv); break;
+  }
+}
+
+// the segments' records, in segment order
+__global__ void __launch_bounds__(64) k_batch_pred_finish(BatchArgs a, BatchPredArgs p) {
+  const int prob = blockIdx.x, tid = threadIdx.x;
+  if (!p.act[prob]) return;
+  if (a.post[(int64_t)prob * a.post_stride + MM * MM + MM + BP_ACTIVE] == 0.0) return;
+  const int seg0 = p.prob_seg[2 * prob], nseg = p.prob_seg[2 * prob + 1];
+  if (tid < 4)
+    p.stats[4 * prob + tid] = rec_sum(p.rec + (int64_t)seg0 * BATCH_PREC + tid, BATCH_PREC, nseg);
+}
+
 }  // namespace
 
 hipError_t launch_batch_eval(const BatchArgs& a, hipStream_t s, hipEvent_t* ev) {
@@ -638,4 +829,25 @@ hipError_t launch_batch_post(const BatchArgs& a, double* res, hipStream_t s) {
   if (a.B < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_batch_post, dim3((unsigned)a.B), dim3(256), 0, s, a, res);
   return hipGetLastError();
+}
+
+hipError_t launch_batch_predict(const BatchArgs& a, const BatchPredArgs& p, hipStream_t s,
+                                hipEvent_t* ev) {
+  if (a.B < 1 || p.nseg < 0 || a.d < 1 || a.d > SGP_MAXD) return hipErrorInvalidValue;
+  hipError_t e = hipSuccess;
+  if (ev && (e = hipEventRecord(ev[0], s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_batch_pred_mm, dim3((unsigned)a.B), dim3(256), 0, s, a, p);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (ev && (e = hipEventRecord(ev[1], s)) != hipSuccess) return e;
+  if (p.nseg > 0) {
+    hipLaunchKernelGGL(k_batch_predict, dim3((unsigned)p.nseg), dim3(256), 0, s, a, p);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if (ev && (e = hipEventRecord(ev[2], s)) != hipSuccess) return e;
+  if (p.score) {
+    hipLaunchKernelGGL(k_batch_pred_finish, dim3((unsigned)a.B), dim3(64), 0, s, a, p);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if (ev) e = hipEventRecord(ev[3], s);
+  return e;
 }

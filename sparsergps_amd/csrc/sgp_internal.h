@@ -639,3 +639,26 @@ struct BatchArgs {
 hipError_t launch_batch_eval(const BatchArgs& a, hipStream_t s, hipEvent_t* ev);
 // res: per problem 64 * 64 + 64 doubles, u_var (row stride 64) | u_mean - muu
 hipError_t launch_batch_post(const BatchArgs& a, double* res, hipStream_t s);
+
+// Batched held-out prediction and scoring (sgp_batch_predict) from the state
+// `post` holds.  A problem's work slot: T = Bm^-1 - K22^-1 (row stride 64) | c0 = (tau^2 +
+// sigma^2) + delta; a test segment's record: the four sgp_nlp stats of its rows.
+constexpr int BPW_C0 = BR_T, BATCH_PW = BR_T + 8, BATCH_PREC = 4;
+struct BatchPredArgs {
+  const double *Xt, *yt, *mut;  // the resident test rows (Xt column-major, ld ldxt); yt may be NULL
+  int64_t ldxt;
+  const int* act;               // B: the problems this call predicts
+  const int* seg_prob;          // per test segment: its problem, its first test row, its rows,
+  const int64_t* seg_row0;      //   and its first row in the packed outputs
+  const int* seg_rows;
+  const int64_t* seg_out;
+  const int* prob_seg;          // per problem: its first segment and its segment count
+  int nseg, score;
+  double* pw;                   // B work slots of BATCH_PW
+  double* rec;                  // nseg records of BATCH_PREC
+  double *pm, *pv, *nlp;        // packed rows
+  double* stats;                // 4 x B
+};
+// ev (or nullptr): 4 events recorded before the m x m stage, the row pass, the finish and after
+hipError_t launch_batch_predict(const BatchArgs& a, const BatchPredArgs& p, hipStream_t s,
+                                hipEvent_t* ev);
