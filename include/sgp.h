@@ -481,6 +481,32 @@ int sgp_batch_eval_vi(sgp_batch* b, int kernel, const double* theta, int64_t ldt
                       int* status);
 int sgp_batch_posterior_u(sgp_batch* b, const double* muu, double* u_mean, double* u_var);
 
+/* sgp_batch_eval_vi with the knot gradient: delbo_dcov_par's knot branch
+ * (R/vi_functions.R:425-593) with dsqexp_dx2 / dsqexp_dx2_ard
+ * (R/covariance_function_derivatives.R:178-302), the derivative kind following `kernel`, as
+ * optimize_gp's xu_opt = "simultaneous" uses it (R/optimize_gp.R:317-333, 396-412).  The
+ * arguments up to status are sgp_batch_eval_vi's, and obj, grad, status and the posterior state
+ * are bit-identical to what sgp_batch_eval_vi gives for them: the same four launches run, and two
+ * more behind them.
+ *   bounds: per problem a d x 2 column-major [lower | upper] block, problem b's at
+ *           bounds + 2 d b: the gradient is with respect to the unbounded knot coordinate of the
+ *           reference's transform, dELBO/du_kc * (ub_c - lb_c) / ((u_kc - lb_c)(ub_c - u_kc) + 1e-4)
+ *           (quirk Q8).  NULL: the factor is 1 and the result is the plain dELBO/du_kc.
+ *   grad_knot: problem b's m[b] d values at grad_knot + uoff[b], knot-major (entry k d + c is knot
+ *           k's coordinate c; quirk Q16) -- U's packing, so U's length serves.
+ * A problem that is not positive definite gets a NaN grad_knot beside its NaN obj and grad; where
+ * active[b] == 0 nothing of problem b's grad_knot is written.  SGP_EINVAL before the first device
+ * call (sgp_diag_batch_knot_args, sgp_diag.h, is the same check) for what sgp_batch_eval_vi
+ * refuses and for a NULL grad_knot, SGP_FLAG_OBJ_ONLY and a non-finite bound of an active problem.
+ * The call makes one copy to the device and one back and allocates nothing.  The fixed-order rule
+ * of sgp_batch_eval_vi covers grad_knot: bit for bit independent of B, the position, the other
+ * problems, `active` and the repeat. */
+int sgp_batch_eval_vi_knots(sgp_batch* b, int kernel, const double* theta, int64_t ldt,
+                            const double* U, const int64_t* uoff, const int64_t* m, double delta,
+                            unsigned flags, const unsigned char* active, double* obj, double* grad,
+                            int64_t ldg, int* status, const double* bounds /* NULL: raw */,
+                            double* grad_knot);
+
 /* Held-out prediction and scoring for a batch: predict_vi
  * (R/vi_functions.R:1222-1336) and my_nlp(family = "gaussian") (R/evaluation_functions.R:14-20,
  * with quirk Q23: pred_var + tau^2 as written) for every problem of the batch in three launches,

@@ -152,6 +152,18 @@ int sgp_diag_batch_plan(const int64_t* row0, const int64_t* nrow, int64_t B, int
 struct sgp_batch;
 int sgp_diag_batch_timing(struct sgp_batch* b, int enable, double* stage_ms);
 
+/* Host only: the checks sgp_batch_eval_vi_knots (sgp.h) makes beyond sgp_batch_eval_vi's, the very
+ * function it runs first: grad_knot NULL, SGP_FLAG_OBJ_ONLY in flags, and a non-finite entry in an
+ * active problem's block of bounds (NULL bounds are allowed).  SGP_OK or SGP_EINVAL with
+ * sgp_last_error() naming the argument. */
+int sgp_diag_batch_knot_args(int d, int64_t B, unsigned flags, const unsigned char* active,
+                             const double* bounds, const double* grad_knot);
+
+/* stage_ms (2 doubles, or NULL): the times by HIP events of the knot pass and the knot finish of
+ * the batch's last sgp_batch_eval_vi_knots (zeros when they were not recorded); enable != 0 records
+ * them from the next such call on.  sgp_diag_batch_timing covers that call's first four stages. */
+int sgp_diag_batch_knot_timing(struct sgp_batch* b, int enable, double* stage_ms);
+
 /* Host only: the argument checks of sgp_batch_set_test (stage 0: d, B and the arguments Xt ..
  * tnrow) and of sgp_batch_predict (stage 1: B and the arguments from have_test on) -- the very
  * function both run before their first device call.  have_test / have_yt: whether set_test was

@@ -1,0 +1,53 @@
+"""k_batch_mm gained a store of H under a run-time flag: show that sgp_batch_eval_vi did not move.
+
+  bit_identity.py dump OUT.npz      obj, grad, status and posterior_u of SparseGPBatch.eval_vi at
+                                    tests/test_gpu_batch.py's MIXED shapes, one batch per
+                                    (d, cov_fun) group, with the library the process loads
+                                    (SGP_AB_LIB=tools/ab/parent/libsgp.so: the parent revision's)
+  bit_identity.py compare A B       np.array_equal of every array of the two dumps
+"""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+
+
+def dump(path):
+    import sparsergps_amd as S
+    from test_gpu_batch import _groups
+    out = {}
+    for (d, cf), Ps in _groups().items():
+        with S.SparseGPBatch.from_problems([(P["X"], P["y"], P["mu"]) for P in Ps]) as b:
+            obj, grad, status = b.eval_vi([P["cov_par"] for P in Ps], cf, [P["U"] for P in Ps],
+                                          1e-6)
+            um, uv = b.posterior_u([np.zeros(P["U"].shape[0]) for P in Ps])
+        out[f"obj_{d}_{cf}"] = obj
+        out[f"status_{d}_{cf}"] = status
+        for i, P in enumerate(Ps):
+            tag = f"{d}_{cf}_{P['X'].shape[0]}_{P['U'].shape[0]}"
+            out[f"grad_{tag}"] = np.array(list(grad[i].values()))
+            out[f"u_mean_{tag}"] = um[i]
+            out[f"u_var_{tag}"] = uv[i]
+    np.savez(path, **out)
+    print("lib", os.environ.get("SGP_AB_LIB", "product"), "arrays", len(out))
+
+
+def compare(a, b):
+    A, B = np.load(a), np.load(b)
+    assert sorted(A.files) == sorted(B.files)
+    bad = [k for k in A.files if not np.array_equal(A[k], B[k], equal_nan=True)]
+    for k in sorted(A.files):
+        print(k, A[k].shape, "DIFFERS" if k in bad else "equal")
+    print(f"{len(A.files) - len(bad)} of {len(A.files)} arrays bit-identical")
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    if sys.argv[1] == "dump":
+        dump(sys.argv[2])
+    else:
+        compare(sys.argv[2], sys.argv[3])

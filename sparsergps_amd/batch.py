@@ -6,6 +6,9 @@
                                one batch evaluation per iteration
   optimize_gp_batch            optimize_gp(family = "gaussian", sparse = TRUE, vi = TRUE,
                                xu_opt = "fixed") for a list of problems
+  SparseGPBatch.eval_vi_knots  the evaluation with every problem's knot gradient (delbo_dcov_par's
+                               knot branch, R/vi_functions.R:425-593), which
+                               xu_opt = "simultaneous" of the three functions above ascends on
   SparseGPBatch.set_test / predict / score
                                predict_vi (R/vi_functions.R:1222-1336) and score_gp's figures for
                                every problem's held-out rows, from the posteriors the batch holds
@@ -13,7 +16,8 @@
   cross_validate_gp            k-fold cross-validation: the folds fitted in lockstep and scored on
                                one batch
 
-Per problem the semantics are the single fit's (drivers._ascent with the knots fixed); a problem
+Per problem the semantics are the single fit's (drivers._ascent, the knots fixed or moved with
+theta: optimize_gp's xu_opt = "fixed" / "simultaneous", R/optimize_gp.R:299-333, 378-412); a problem
 that meets its stop rule is retired through the evaluation's `active` mask while the others go
 on.  The path is opt-in: nothing else in the package routes to it.
 """
@@ -26,8 +30,8 @@ import numpy as np
 
 from . import _lib
 from .covariance import theta_vector
-from .drivers import _opts
-from .vi import param_names
+from .drivers import _opts, _unbounded
+from .vi import knot_bounds, param_names
 
 MMAX = _lib.SGP_BATCH_MMAX
 
@@ -114,6 +118,12 @@ class SparseGPBatch:
         of m_b x d knot arrays (entries of inactive problems may be None), active a uint8 array
         or None, obj (B), grad (B x P, or None with SGP_FLAG_OBJ_ONLY), status (B, int32).
         Slots of inactive problems are left as they are."""
+        self._eval(cov_fun, theta, xus, delta, flags, active, obj, grad, status)
+
+    def _eval(self, cov_fun, theta, xus, delta, flags, active, obj, grad, status, knots=False,
+              bounds=None):
+        """sgp_batch_eval_vi, or with knots sgp_batch_eval_vi_knots (bounds: B x 2d or None);
+        returns (grad_knot packed like U, uoff, m) with knots."""
         self._need()
         theta = np.ascontiguousarray(theta, dtype=np.float64)
         on = [active is None or bool(active[b]) for b in range(self.B)]
@@ -127,16 +137,24 @@ class SparseGPBatch:
         U = np.concatenate(packs + [np.zeros(1)])
         act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
         i64 = lambda a: a.ctypes.data_as(_lib.c_int64_p)   # noqa: E731
-        st = self._lib.sgp_batch_eval_vi(
-            self._h, _lib.KERNELS.get(cov_fun, -1), _lib.dptr(theta), theta.shape[1], _lib.dptr(U),
-            i64(uoff), i64(m), float(delta), int(flags),
-            None if act is None else act.ctypes.data_as(_lib.c_ubyte_p), _lib.dptr(obj),
-            None if grad is None else _lib.dptr(grad), 0 if grad is None else grad.shape[1],
-            status.ctypes.data_as(_lib.c_int_p))
+        args = (self._h, _lib.KERNELS.get(cov_fun, -1), _lib.dptr(theta), theta.shape[1],
+                _lib.dptr(U), i64(uoff), i64(m), float(delta), int(flags),
+                None if act is None else act.ctypes.data_as(_lib.c_ubyte_p), _lib.dptr(obj),
+                None if grad is None else _lib.dptr(grad), 0 if grad is None else grad.shape[1],
+                status.ctypes.data_as(_lib.c_int_p))
+        gk = None
+        if knots:
+            gk = np.full(U.size, np.nan)
+            bd = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.float64)
+            st = self._lib.sgp_batch_eval_vi_knots(*args, None if bd is None else _lib.dptr(bd),
+                                                   _lib.dptr(gk))
+        else:
+            st = self._lib.sgp_batch_eval_vi(*args)
         _lib.check(st)
         for b in range(self.B):
             if on[b] and status[b] == 0:
                 self._state[b] = int(m[b])
+        return gk, uoff, m
 
     def eval_vi(self, cov_pars, cov_fun, xus, delta=1e-6, active=None, obj_only=False,
                 r_det=False):
@@ -156,6 +174,9 @@ class SparseGPBatch:
         status = np.zeros(self.B, dtype=np.int32)
         flags = (_lib.SGP_FLAG_OBJ_ONLY if obj_only else 0) | (_lib.SGP_FLAG_R_DET if r_det else 0)
         self.eval_raw(cov_fun, theta, xus, delta, flags, active, obj, g, status)
+        return obj, self._named(cov_pars, cov_fun, g, on), status
+
+    def _named(self, cov_pars, cov_fun, g, on):
         names = param_names(cov_fun, self.d)
         grads = []
         for b in range(self.B):
@@ -164,7 +185,64 @@ class SparseGPBatch:
                 continue
             byname = dict(zip(names, g[b]))
             grads.append(OrderedDict((k, float(byname[k])) for k in cov_pars[b].keys()))
-        return obj, grads, status
+        return grads
+
+    def knot_bounds(self):
+        """knot_bounds (vi_functions.R:175-178) of each problem's own rows: B arrays of d x 2.
+        Computed once; set_data replaces y and mu only, so it does not invalidate them."""
+        if getattr(self, "_kb", None) is None:
+            self._kb = [knot_bounds(self.rows(b)[0]) for b in range(self.B)]
+        return self._kb
+
+    def eval_vi_knots(self, cov_pars, cov_fun, xus, delta=1e-6, active=None, bounds="data",
+                      r_det=False):
+        """eval_vi with every active problem's knot gradient (sgp_batch_eval_vi_knots).  Returns
+        (obj, grads, knot_grads, status): obj, grads and status are eval_vi's, bit for bit;
+        knot_grads[b] is the (m_b d,) knot-major vector (entry k d + c: knot k, coordinate c) of
+        dsqexp_dx2 / dsqexp_dx2_ard following cov_fun, None for an inactive problem and NaN for
+        one that is not positive definite.  bounds: "data" for knot_bounds of each problem's own
+        rows (the drivers' choice), None for the plain dELBO/du, or a list of B d x 2 arrays
+        (entries of inactive problems may be None)."""
+        P = (self.d if cov_fun == "ard" else 1) + 2
+        theta = np.ones((self.B, P))
+        on = [active is None or bool(active[b]) for b in range(self.B)]
+        for b in range(self.B):
+            if on[b]:
+                theta[b] = theta_vector(cov_pars[b], cov_fun, self.d)
+        if isinstance(bounds, str):
+            if bounds != "data":
+                raise ValueError(f'eval_vi_knots: bounds must be "data", None or a list, not '
+                                 f"{bounds!r}")
+            bounds = self.knot_bounds()
+        bd = None
+        if bounds is not None:
+            if len(bounds) != self.B:
+                raise ValueError(f"eval_vi_knots: {len(bounds)} bounds for {self.B} problems")
+            bd = np.zeros((self.B, 2 * self.d))
+            for b in range(self.B):
+                if on[b]:
+                    bb = np.asarray(bounds[b], dtype=np.float64)
+                    if bb.shape != (self.d, 2):
+                        raise ValueError(f"problem {b}: bounds are not {self.d} x 2")
+                    bd[b] = bb.reshape(-1, order="F")
+        obj = np.full(self.B, np.nan)
+        g = np.full((self.B, P), np.nan)
+        status = np.zeros(self.B, dtype=np.int32)
+        flags = _lib.SGP_FLAG_R_DET if r_det else 0
+        gk, uoff, m = self._eval(cov_fun, theta, xus, delta, flags, active, obj, g, status,
+                                 knots=True, bounds=bd)
+        kg = [gk[uoff[b]:uoff[b] + m[b] * self.d].copy() if on[b] else None
+              for b in range(self.B)]
+        return obj, self._named(cov_pars, cov_fun, g, on), kg, status
+
+    def knot_stage_ms(self, enable=True):
+        """HIP-event times (ms) of the last eval_vi_knots' knot pass and knot finish; records from
+        the next one on (stage_ms covers its first four stages)."""
+        self._need()
+        out = np.zeros(2)
+        _lib.check(self._lib.sgp_diag_batch_knot_timing(self._h, int(bool(enable)),
+                                                        _lib.dptr(out)))
+        return out
 
     def posterior_u(self, muus):
         """(u_mean list, u_var list): the knot posterior of each problem's last successful
@@ -344,29 +422,75 @@ def _not_pd(status):
                          "not positive definite")
 
 
+def _xu_opt(xu_opt, who):
+    """True for "simultaneous", False for "fixed"; optimize_gp's refusals otherwise."""
+    if xu_opt == "fixed":
+        return False
+    if xu_opt in ("oat", "random"):
+        raise ValueError(f'{who}: batches do not support xu_opt = "{xu_opt}" (the knot search '
+                         'adds and removes knots problem by problem); use optimize_gp')
+    if xu_opt != "simultaneous":
+        raise ValueError(f'{who}: xu_opt must be "fixed" or "simultaneous", not {xu_opt!r}')
+    return True
+
+
 def norm_grad_ascent_vi_batch(cov_par_starts, cov_fun, xus, batch, muus=None, opt=None,
-                              dcov_fun_dknot=None):
+                              dcov_fun_dknot=None, xu_opt="fixed", knot_opt=None):
     """B norm_grad_ascent_vi runs in lockstep on one batch: every iteration is one
-    batch.eval_vi call over the problems still running.  batch: a SparseGPBatch, or a list of
-    (xy, y, mu) problems to build one from.  Returns a list of the dicts norm_grad_ascent_vi
-    returns; a problem whose evaluation is not positive definite retires with that error under
-    "error" (the R error the single fit raises) and u_mean = u_var = None."""
+    batch.eval_vi call over the problems still running (one batch.eval_vi_knots call with
+    xu_opt = "simultaneous").  batch: a SparseGPBatch, or a list of (xy, y, mu) problems to build
+    one from.  Returns a list of the dicts norm_grad_ascent_vi returns; a problem whose evaluation
+    is not positive definite retires with that error under "error" (the R error the single fit
+    raises) and u_mean = u_var = None.
+
+    xu_opt = "simultaneous" moves every problem's knots with its theta as drivers._ascent does
+    (the knot derivative kind follows cov_fun, the bounded transform is on knot_bounds of the
+    problem's own rows); knot_opt: the 1-based knots that move, one list for all problems or one
+    per problem (None: all), the others' gradient being zero."""
     if not (dcov_fun_dknot is None or dcov_fun_dknot is False or
             (isinstance(dcov_fun_dknot, float) and np.isnan(dcov_fun_dknot))):
-        raise ValueError("norm_grad_ascent_vi_batch: knot gradients are not supported "
-                         "(dcov_fun_dknot must be None)")
+        raise ValueError("norm_grad_ascent_vi_batch: knot gradients are not supported through "
+                         'dcov_fun_dknot (it must be None); pass xu_opt = "simultaneous"')
+    simul = _xu_opt(xu_opt, "norm_grad_ascent_vi_batch")
     o = _opts(opt)
     own = not hasattr(batch, "eval_vi")
     if own:
         batch = SparseGPBatch.from_problems(batch)
     try:
-        return _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o)
+        return _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o, simul, knot_opt)
     finally:
         if own:
             batch.close()
 
 
-def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o):
+def _bounded(t, bounds):
+    """drivers._bounded in the reference's order of operations, a product with the reciprocal
+    (trans_fun, covariance_function_derivatives.R:191-197): a last-bit difference in a knot shows
+    at 1e-11 in the knot gradient's small entries.  t: d values or m x d."""
+    return bounds[:, 1] * (1 / (1 + np.exp(-t))) + bounds[:, 0] * (1 / (1 + np.exp(t)))
+
+
+def _knot_keep(knot_opt, B, ms, d):
+    """Per problem the 0 / 1 factor of its knot-major gradient, or None where every knot moves."""
+    if knot_opt is None:
+        return [None] * B
+    ko = list(knot_opt)
+    nested = any(k is None or np.ndim(k) > 0 for k in ko)   # one list per problem
+    per = ko if nested else [ko] * B
+    if len(per) != B:
+        raise ValueError(f"norm_grad_ascent_vi_batch: {len(per)} knot_opt lists for {B} problems")
+    out = []
+    for b in range(B):
+        if per[b] is None:
+            out.append(None)
+            continue
+        keep = np.zeros(ms[b], dtype=bool)
+        keep[np.asarray(list(per[b]), dtype=int) - 1] = True
+        out.append(np.repeat(keep, d).astype(np.float64))
+    return out
+
+
+def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o, simul=False, knot_opt=None):
     B = batch.B
     if len(cov_par_starts) != B or len(xus) != B:
         raise ValueError(f"norm_grad_ascent_vi_batch: {B} problems, {len(cov_par_starts)} "
@@ -390,10 +514,23 @@ def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o):
     error = [None] * B
     active = np.ones(B, dtype=np.uint8)
     adadelta = o["optim_method"] == "adadelta"
+    # the knot state of drivers._ascent, per problem
+    gk = [np.zeros(0)] * B
+    if simul:
+        bounds = [knot_bounds(data[b][0]) for b in range(B)]
+        keep = _knot_keep(knot_opt, B, [u.shape[0] for u in xus], d)
+        xu_t = [_unbounded(xus[b], bounds[b]) for b in range(B)]
+        sg2k, sd2k, sck = ([np.zeros(xus[b].size) for b in range(B)] for _ in range(3))
+        tr_kg = [[] for _ in range(B)]
+        tr_xu = [[xus[b].copy()] for b in range(B)]
 
     def evaluate(first):
         pars = [OrderedDict(zip(names[b], cur[b])) for b in range(B)]
-        ob, gr, st = batch.eval_vi(pars, cov_fun, xus, o["delta"], active=active)
+        if simul:
+            ob, gr, kg, st = batch.eval_vi_knots(pars, cov_fun, xus, o["delta"], active=active,
+                                                 bounds=bounds)
+        else:
+            ob, gr, st = batch.eval_vi(pars, cov_fun, xus, o["delta"], active=active)
         for b in range(B):
             if not active[b]:
                 continue
@@ -405,6 +542,15 @@ def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o):
             if not first and adadelta:
                 sc[b] = o["decay"] * sc[b] + (1 - o["decay"]) * np.abs(np.sign(gnew) -
                                                                       np.sign(gt[b])) / 2
+            if simul:
+                gknew = np.asarray(kg[b], dtype=np.float64)
+                if keep[b] is not None:
+                    gknew = gknew * keep[b]
+                if not first and adadelta:      # not halved, unlike theta's (drivers._ascent)
+                    sck[b] = o["decay"] * sck[b] + (1 - o["decay"]) * np.abs(np.sign(gknew) -
+                                                                            np.sign(gk[b]))
+                gk[b] = gknew
+                tr_kg[b].append(gknew)
             obj[b], gt[b] = float(ob[b]), gnew
             tr_obj[b].append(obj[b])
             tr_cov[b].append(cur[b].copy())
@@ -418,7 +564,7 @@ def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o):
                 continue
             k = it[b]
             if not (k < o["maxit"] and (
-                    bool(np.any(np.abs(gt[b]) > o["grad_tol"])) or
+                    bool(np.any(np.abs(np.concatenate([gt[b], gk[b]])) > o["grad_tol"])) or
                     (abs(obj[b] - tr_obj[b][k - 2]) > o["obj_tol"] if k > 1 else True))):
                 active[b] = 0                       # retired: never evaluated again
                 continue
@@ -431,6 +577,17 @@ def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o):
             else:
                 step = o["learn_rate"] * gt[b]
             log_t[b] = log_t[b] + step
+            if simul:
+                if adadelta:
+                    sg2k[b] = o["decay"] * sg2k[b] + (1 - o["decay"]) * gk[b] ** 2
+                    step_k = ((1 / o["eta"]) ** sck[b]) * (np.sqrt(sd2k[b] + o["epsilon"]) /
+                                                           np.sqrt(sg2k[b] + o["epsilon"])) * gk[b]
+                    sd2k[b] = o["decay"] * sd2k[b] + (1 - o["decay"]) * step_k ** 2
+                else:
+                    step_k = o["learn_rate"] * gk[b]
+                xu_t[b] = xu_t[b] + step_k.reshape(xus[b].shape)     # knot-major (Q16)
+                xus[b] = _bounded(xu_t[b], bounds[b])                # every knot row at once
+                tr_xu[b].append(xus[b].copy())
             cur[b] = np.exp(log_t[b])
         if not active.any():
             break
@@ -444,7 +601,9 @@ def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o):
         xy, _, mu = data[b]
         res = {"cov_par": OrderedDict(zip(names[b], cur[b])), "xu": xus[b], "iter": it[b],
                "obj_fun": np.array(tr_obj[b]), "grad": np.array(tr_grad[b]),
-               "cov_par_history": np.array(tr_cov[b]), "knot_grad": 0, "knot_history": xus[b],
+               "cov_par_history": np.array(tr_cov[b]),
+               "knot_grad": np.array(tr_kg[b]) if simul else 0,
+               "knot_history": np.stack(tr_xu[b], axis=2) if simul else xus[b],
                "cov_fun": cov_fun, "xy": np.array(xy), "mu": np.array(mu), "muu": muus[b],
                "u_mean": None if error[b] else u_means[b],
                "u_var": None if error[b] else u_vars[b]}
@@ -477,13 +636,19 @@ def _knots_and_muu(xu, muu):
     return u, np.asarray(muu, dtype=np.float64).reshape(-1)
 
 
-def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None):
+_ERR_Q10 = ('xu_opt = "simultaneous" passes cov_fun = "sqexp" to the driver '
+            '(R/optimize_gp.R:320, 399), which cannot take an "ard" fit\'s cov_par; use "fixed"')
+
+
+def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None, xu_opt="fixed"):
     """optimize_gp(y, xy, cov_fun, cov_par_start, mu, family = "gaussian", sparse = TRUE,
-    xu_opt = "fixed", xu, muu, vi = TRUE, opt) for each (xy, y, mu) of `problems`, fitted in
-    lockstep on one batch.  cov_par_start, xu and muu: one value for all problems or a list with
+    xu_opt, xu, muu, vi = TRUE, opt) for each (xy, y, mu) of `problems`, fitted in lockstep on
+    one batch.  xu_opt: "fixed" or "simultaneous" (all knots move, R/optimize_gp.R:396-412; with
+    cov_fun = "ard" optimize_gp's quirk-Q10 ValueError); "oat" and "random" are refused.  cov_par_start, xu and muu: one value for all problems or a list with
     one per problem.  Returns a list of optimize_gp's {"results", "sparse", "family", "delta",
     "xu_init"} dicts (or its error strings), which predict_gp, predictor_gp and score_gp take."""
     from .optimize import ERR_COV, ERR_GA, ERR_MAXKNOT, OPT_MASTER
+    simul = _xu_opt(xu_opt, "optimize_gp_batch")
     B = len(problems)
     o = {k: (dict(v) if isinstance(v, dict) else v) for k, v in OPT_MASTER.items()}
     for k, v in (opt or {}).items():
@@ -493,6 +658,8 @@ def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None):
         return [ERR_GA] * B
     if cov_fun not in ("sqexp", "ard"):
         return [ERR_COV] * B
+    if simul and cov_fun == "ard":
+        raise ValueError(_ERR_Q10)
     starts, xus, muus = _per_problem(B, cov_par_start, xu, muu, "optimize_gp_batch", "problem")
     out, keep = [None] * B, []
     for b, prob in enumerate(problems):
@@ -506,7 +673,7 @@ def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None):
     if keep:
         res = norm_grad_ascent_vi_batch([starts[b] for b, *_ in keep], cov_fun,
                                         [u for _, _, u, _ in keep], [p for _, p, _, _ in keep],
-                                        [mb for *_, mb in keep], o)
+                                        [mb for *_, mb in keep], o, xu_opt=xu_opt)
         for (b, _, u, _), r in zip(keep, res):
             out[b] = {"results": r, "sparse": True, "family": "gaussian", "delta": o["delta"],
                       "xu_init": u}
@@ -514,10 +681,12 @@ def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None):
 
 
 def cross_validate_gp(y, xy, cov_fun, cov_par_start, xu, folds=5, mu=None, muu=None, opt=None,
-                      rng=None):
+                      rng=None, xu_opt="fixed"):
     """k-fold cross-validation of optimize_gp(family = "gaussian", sparse = TRUE, vi = TRUE,
-    xu_opt = "fixed"): every fold's fit runs in lockstep on one batch and every fold's held-out
-    rows are scored on it (SparseGPBatch.score), without the posteriors leaving the device.
+    xu_opt): every fold's fit runs in lockstep on one batch and every fold's held-out rows are
+    scored on it (SparseGPBatch.score), without the posteriors leaving the device.  xu_opt is
+    optimize_gp_batch's: "fixed", or "simultaneous" for folds whose knots move (each on
+    knot_bounds of its own training rows); the scores then use the moved knots.
 
     folds: an integer (a random partition from rng, default np.random.default_rng(0)) or an
     integer array of fold ids, one per row.  Fold f trains on the rows of every other fold and
@@ -531,6 +700,7 @@ def cross_validate_gp(y, xy, cov_fun, cov_par_start, xu, folds=5, mu=None, muu=N
     "mean_nlp", "median_nlp" (over all held-out rows' finite nlp), "rmse" (over all held-out
     rows), "fold_id"}; the pooled figures cover the folds that were scored."""
     from .optimize import ERR_COV, ERR_GA, ERR_MAXKNOT, OPT_MASTER
+    simul = _xu_opt(xu_opt, "cross_validate_gp")
     y = np.asarray(y, dtype=np.float64).reshape(-1)
     n = y.size
     xy = _mat(xy, n)
@@ -542,6 +712,8 @@ def cross_validate_gp(y, xy, cov_fun, cov_par_start, xu, folds=5, mu=None, muu=N
         return ERR_GA
     if cov_fun not in ("sqexp", "ard"):
         return ERR_COV
+    if simul and cov_fun == "ard":
+        raise ValueError(_ERR_Q10)
     if np.ndim(folds) == 0:
         k = int(folds)
         if not 2 <= k <= n:
@@ -575,7 +747,7 @@ def cross_validate_gp(y, xy, cov_fun, cov_par_start, xu, folds=5, mu=None, muu=N
         mbs.append(mb)
     batch = SparseGPBatch.from_problems(problems)
     try:
-        res = norm_grad_ascent_vi_batch(starts, cov_fun, us, batch, mbs, o)
+        res = norm_grad_ascent_vi_batch(starts, cov_fun, us, batch, mbs, o, xu_opt=xu_opt)
         ok = np.array(["error" not in r for r in res], dtype=np.uint8)
         scores = [None] * B
         if ok.any():

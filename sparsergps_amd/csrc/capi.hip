@@ -5257,6 +5257,12 @@ struct sgp_batch {
   int *seg_prob = nullptr, *seg_rows = nullptr;
   int64_t* seg_row0 = nullptr;
   double *h_par = nullptr, *h_out = nullptr;   // pinned
+  // sgp_batch_eval_vi_knots (sec. 0p): par and h_par end in B bound blocks of 2 d, out and h_out
+  // in the packed knot gradients (up to 64 d per problem), so a call is one copy each way
+  double *hk = nullptr, *rec3 = nullptr;
+  hipEvent_t kev[3] = {nullptr, nullptr, nullptr};
+  float kstage_ms[2] = {0.f, 0.f};
+  bool ktiming = false;
   std::vector<int64_t> row0, nrow, seg0, nsegs, last_m;
   std::vector<char> has_state;
   int last_ard = 0;
@@ -5364,6 +5370,33 @@ int batch_check_eval(int d, int64_t B, int kernel, const double* theta, int64_t 
       return SGP_EINVAL;
     }
   }
+  return SGP_OK;
+}
+
+// What sgp_batch_eval_vi_knots checks beyond batch_check_eval; sgp_diag_batch_knot_args is this
+// function.
+int batch_check_knots(int d, int64_t B, unsigned flags, const unsigned char* active,
+                      const double* bounds, const double* grad_knot) {
+  if (B < 1 || d < 1 || d > SGP_MAXD) {
+    set_err("sgp_batch_eval_vi_knots: B=%lld, d=%d", (long long)B, d);
+    return SGP_EINVAL;
+  }
+  if (!grad_knot) { set_err("sgp_batch_eval_vi_knots: grad_knot must not be NULL"); return SGP_EINVAL; }
+  if (flags & SGP_FLAG_OBJ_ONLY) {
+    set_err("sgp_batch_eval_vi_knots: flags has SGP_FLAG_OBJ_ONLY (the knot gradient needs the "
+            "second row pass)");
+    return SGP_EINVAL;
+  }
+  if (bounds)
+    for (int64_t b = 0; b < B; ++b) {
+      if (active && !active[b]) continue;
+      int64_t bad = 0;
+      if (!finite_all(bounds + 2 * d * b, 2 * d, &bad)) {
+        set_err("sgp_batch_eval_vi_knots: problem %lld's bounds[%lld, %lld] is not finite",
+                (long long)b, (long long)(bad % d), (long long)(bad / d));
+        return SGP_EINVAL;
+      }
+    }
   return SGP_OK;
 }
 
@@ -5487,8 +5520,10 @@ void batch_free(sgp_batch* b) {
   batch_free_test(b);
   for (hipEvent_t e : b->pev)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : b->kev)
+    if (e) (void)hipEventDestroy(e);
   for (double* p : {b->X, b->y, b->mu, b->par, b->rec1, b->rec2, b->pm, b->sc, b->out, b->post,
-                    b->res})
+                    b->res, b->hk, b->rec3})
     if (p) (void)hipFree(p);
   if (b->seg_prob) (void)hipFree(b->seg_prob);
   if (b->seg_rows) (void)hipFree(b->seg_rows);
@@ -5509,6 +5544,7 @@ BatchArgs batch_args(const sgp_batch* b, int ard, int obj_only) {
   a.seg_prob = b->seg_prob; a.seg_row0 = b->seg_row0; a.seg_rows = b->seg_rows;
   a.rec1 = b->rec1; a.rec2 = b->rec2; a.pm = b->pm; a.sc = b->sc; a.out = b->out;
   a.post = b->post; a.post_stride = b->post_stride;
+  a.hk = nullptr; a.rec3 = nullptr; a.bnd = nullptr; a.gk = nullptr;
   return a;
 }
 
@@ -5531,22 +5567,26 @@ int batch_create_impl(sgp_batch* b, const double* X, int64_t ldx, const double* 
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
   for (hipEvent_t& e : b->ev) HIPCHK(hipEventCreate(&e));
+  for (hipEvent_t& e : b->kev) HIPCHK(hipEventCreate(&e));
+  const int64_t gcap = B * SGP_BATCH_MMAX * d;   // the packed knot gradients at their largest
   HIPCHK(hipMalloc(&b->X, sizeof(double) * n * d));
   HIPCHK(hipMalloc(&b->y, sizeof(double) * n));
   HIPCHK(hipMalloc(&b->mu, sizeof(double) * n));
-  HIPCHK(hipMalloc(&b->par, sizeof(double) * B * b->pst));
+  HIPCHK(hipMalloc(&b->par, sizeof(double) * B * (b->pst + 2 * d)));
   HIPCHK(hipMalloc(&b->rec1, sizeof(double) * b->nseg * BATCH_REC1));
   HIPCHK(hipMalloc(&b->rec2, sizeof(double) * b->nseg * BATCH_REC2));
   HIPCHK(hipMalloc(&b->pm, sizeof(double) * B * BATCH_PM));
   HIPCHK(hipMalloc(&b->sc, sizeof(double) * B * BATCH_SC));
-  HIPCHK(hipMalloc(&b->out, sizeof(double) * B * BATCH_OUT));
+  HIPCHK(hipMalloc(&b->out, sizeof(double) * (B * BATCH_OUT + gcap)));
+  HIPCHK(hipMalloc(&b->hk, sizeof(double) * B * BR_T));
+  HIPCHK(hipMalloc(&b->rec3, sizeof(double) * b->nseg * BATCH_REC3));
   HIPCHK(hipMalloc(&b->post, sizeof(double) * B * b->post_stride));
   HIPCHK(hipMalloc(&b->res, sizeof(double) * B * (BR_T + SGP_BATCH_MMAX)));
   HIPCHK(hipMalloc(&b->seg_prob, sizeof(int) * b->nseg));
   HIPCHK(hipMalloc(&b->seg_rows, sizeof(int) * b->nseg));
   HIPCHK(hipMalloc(&b->seg_row0, sizeof(int64_t) * b->nseg));
-  HIPCHK(hipHostMalloc(&b->h_par, sizeof(double) * B * b->pst));
-  HIPCHK(hipHostMalloc(&b->h_out, sizeof(double) * B * BATCH_OUT));
+  HIPCHK(hipHostMalloc(&b->h_par, sizeof(double) * B * (b->pst + 2 * d)));
+  HIPCHK(hipHostMalloc(&b->h_out, sizeof(double) * (B * BATCH_OUT + gcap)));
   HIPCHK(hipMemsetAsync(b->post, 0, sizeof(double) * B * b->post_stride, b->stream));
   HIPCHK(hipMemsetAsync(b->out, 0, sizeof(double) * B * BATCH_OUT, b->stream));
   HIPCHK(hipMemcpy2DAsync(b->X, sizeof(double) * n, X, sizeof(double) * ldx, sizeof(double) * n,
@@ -5667,17 +5707,20 @@ int sgp_batch_set_data(sgp_batch* b, const double* y, const double* mu) {
   return SGP_OK;
 }
 
-int sgp_batch_eval_vi(sgp_batch* b, int kernel, const double* theta, int64_t ldt, const double* U,
-                      const int64_t* uoff, const int64_t* m, double delta, unsigned flags,
-                      const unsigned char* active, double* obj, double* grad, int64_t ldg,
-                      int* status) {
-  if (!b) { set_err("sgp_batch_eval_vi: the sgp_batch is NULL"); return SGP_EINVAL; }
-  const int cst = batch_check_eval(b->d, b->B, kernel, theta, ldt, U, uoff, m, delta, flags,
-                                   active, obj, grad, ldg, status);
-  if (cst != SGP_OK) return cst;
+}  // extern "C"
+
+namespace {
+
+// sgp_batch_eval_vi (grad_knot = nullptr) and sgp_batch_eval_vi_knots after their checks: the
+// same four launches on the same arguments, and with grad_knot the two knot launches behind them
+int batch_eval_impl(sgp_batch* b, int kernel, const double* theta, int64_t ldt, const double* U,
+                    const int64_t* uoff, const int64_t* m, double delta, unsigned flags,
+                    const unsigned char* active, double* obj, double* grad, int64_t ldg,
+                    int* status, const double* bounds, double* grad_knot) {
   const int d = b->d, ard = kernel == SGP_KERNEL_ARD, L = ard ? d : 1, P = L + 2;
   const bool obj_only = flags & SGP_FLAG_OBJ_ONLY;
   bool any = false;
+  int64_t gtot = 0;   // the packed knot gradients: the active problems' m d values in order
   for (int64_t p = 0; p < b->B; ++p) {
     double* h = b->h_par + p * b->pst;
     const bool on = !active || active[p];
@@ -5695,6 +5738,8 @@ int sgp_batch_eval_vi(sgp_batch* b, int kernel, const double* theta, int64_t ldt
     h[BP_RDET] = (flags & SGP_FLAG_R_DET) ? 1.0 : 0.0;
     h[BP_SEG0] = (double)b->seg0[(size_t)p];
     h[BP_NSEG] = (double)b->nsegs[(size_t)p];
+    h[BP_GOFF] = (double)gtot;
+    gtot += m[p] * d;
     for (int c = 0; c < d; ++c) h[BP_RL + c] = 1.0 / th[1 + (ard ? c : 0)];
     const double* u = U + uoff[p];
     for (int c = 0; c < d; ++c)
@@ -5702,16 +5747,30 @@ int sgp_batch_eval_vi(sgp_batch* b, int kernel, const double* theta, int64_t ldt
         h[BP_U + c * SGP_BATCH_MMAX + j] = j < m[p] ? u[(int64_t)c * m[p] + j] : 0.0;
   }
   if (!any) return SGP_OK;
+  const int64_t npar = b->B * b->pst;
+  if (grad_knot && bounds) std::copy(bounds, bounds + b->B * 2 * d, b->h_par + npar);
   HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipMemcpyAsync(b->par, b->h_par, sizeof(double) * b->B * b->pst, hipMemcpyHostToDevice,
-                        b->stream));
-  const BatchArgs a = batch_args(b, ard, obj_only ? 1 : 0);
+  HIPCHK(hipMemcpyAsync(b->par, b->h_par,
+                        sizeof(double) * (npar + (grad_knot && bounds ? b->B * 2 * d : 0)),
+                        hipMemcpyHostToDevice, b->stream));
+  BatchArgs a = batch_args(b, ard, obj_only ? 1 : 0);
+  if (grad_knot) {
+    a.hk = b->hk;
+    a.rec3 = b->rec3;
+    a.bnd = bounds ? b->par + npar : nullptr;
+    a.gk = b->out + b->B * BATCH_OUT;
+  }
   HIPCHK(launch_batch_eval(a, b->stream, b->timing ? b->ev : nullptr));
-  HIPCHK(hipMemcpyAsync(b->h_out, b->out, sizeof(double) * b->B * BATCH_OUT,
+  if (grad_knot) HIPCHK(launch_batch_knots(a, b->stream, b->ktiming ? b->kev : nullptr));
+  HIPCHK(hipMemcpyAsync(b->h_out, b->out,
+                        sizeof(double) * (b->B * BATCH_OUT + (grad_knot ? gtot : 0)),
                         hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
   if (b->timing)
     for (int q = 0; q < 4; ++q) HIPCHK(hipEventElapsedTime(&b->stage_ms[q], b->ev[q], b->ev[q + 1]));
+  if (grad_knot && b->ktiming)
+    for (int q = 0; q < 2; ++q)
+      HIPCHK(hipEventElapsedTime(&b->kstage_ms[q], b->kev[q], b->kev[q + 1]));
   b->last_ard = ard;
   bool failed = false;
   for (int64_t p = 0; p < b->B; ++p) {
@@ -5723,6 +5782,8 @@ int sgp_batch_eval_vi(sgp_batch* b, int kernel, const double* theta, int64_t ldt
       obj[p] = NAN;
       if (grad)
         for (int q = 0; q < P; ++q) grad[p * ldg + q] = NAN;
+      if (grad_knot)
+        for (int64_t q = 0; q < m[p] * d; ++q) grad_knot[uoff[p] + q] = NAN;
       if (!failed)
         set_err("problem %lld: chol(): the leading minor of order %d of %s is not positive definite",
                 (long long)p, st > 0 ? st : -st,
@@ -5733,9 +5794,58 @@ int sgp_batch_eval_vi(sgp_batch* b, int kernel, const double* theta, int64_t ldt
     obj[p] = o[0];
     if (!obj_only)
       for (int q = 0; q < P; ++q) grad[p * ldg + q] = o[2 + q];
+    if (grad_knot) {
+      const double* gk = b->h_out + b->B * BATCH_OUT + (int64_t)b->h_par[p * b->pst + BP_GOFF];
+      std::copy(gk, gk + m[p] * d, grad_knot + uoff[p]);
+    }
     b->has_state[(size_t)p] = 1;
     b->last_m[(size_t)p] = m[p];
   }
+  return SGP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sgp_batch_eval_vi(sgp_batch* b, int kernel, const double* theta, int64_t ldt, const double* U,
+                      const int64_t* uoff, const int64_t* m, double delta, unsigned flags,
+                      const unsigned char* active, double* obj, double* grad, int64_t ldg,
+                      int* status) {
+  if (!b) { set_err("sgp_batch_eval_vi: the sgp_batch is NULL"); return SGP_EINVAL; }
+  const int cst = batch_check_eval(b->d, b->B, kernel, theta, ldt, U, uoff, m, delta, flags,
+                                   active, obj, grad, ldg, status);
+  if (cst != SGP_OK) return cst;
+  return batch_eval_impl(b, kernel, theta, ldt, U, uoff, m, delta, flags, active, obj, grad, ldg,
+                         status, nullptr, nullptr);
+}
+
+int sgp_diag_batch_knot_args(int d, int64_t B, unsigned flags, const unsigned char* active,
+                             const double* bounds, const double* grad_knot) {
+  return batch_check_knots(d, B, flags, active, bounds, grad_knot);
+}
+
+int sgp_batch_eval_vi_knots(sgp_batch* b, int kernel, const double* theta, int64_t ldt,
+                            const double* U, const int64_t* uoff, const int64_t* m, double delta,
+                            unsigned flags, const unsigned char* active, double* obj, double* grad,
+                            int64_t ldg, int* status, const double* bounds, double* grad_knot) {
+  if (!b) { set_err("sgp_batch_eval_vi_knots: the sgp_batch is NULL"); return SGP_EINVAL; }
+  int cst = batch_check_knots(b->d, b->B, flags, active, bounds, grad_knot);
+  if (cst != SGP_OK) return cst;
+  cst = batch_check_eval(b->d, b->B, kernel, theta, ldt, U, uoff, m, delta, flags, active, obj,
+                         grad, ldg, status);
+  if (cst != SGP_OK) return cst;
+  return batch_eval_impl(b, kernel, theta, ldt, U, uoff, m, delta, flags, active, obj, grad, ldg,
+                         status, bounds, grad_knot);
+}
+
+/* stage_ms (2 doubles, or NULL): the HIP-event times of the knot pass and the knot finish of the
+ * last sgp_batch_eval_vi_knots; enable != 0 records them from the next such call on. */
+int sgp_diag_batch_knot_timing(sgp_batch* b, int enable, double* stage_ms) {
+  if (!b) { set_err("sgp_diag_batch_knot_timing: the sgp_batch is NULL"); return SGP_EINVAL; }
+  if (stage_ms)
+    for (int q = 0; q < 2; ++q) stage_ms[q] = b->ktiming ? (double)b->kstage_ms[q] : 0.0;
+  b->ktiming = enable != 0;
   return SGP_OK;
 }
 

@@ -20,6 +20,9 @@
 // Held-out prediction and scoring from that state (sgp_batch_predict), below
 // the evaluation's kernels: k_batch_pred_mm per problem, k_batch_predict per test segment,
 // k_batch_pred_finish per problem, under the same rules.
+// The knot gradient (sgp_batch_eval_vi_knots) at the end of the file:
+// k_batch_knot_pass per segment and k_batch_knot_finish per problem, after the evaluation's four
+// launches, under the same rules again.
 #include <math.h>
 
 #include "sgp_internal.h"
@@ -358,6 +361,11 @@ __global__ void __launch_bounds__(256) k_batch_mm(BatchArgs a) {
     Bm[i * MM + j] = g22 * kuu;   // H: each thread rewrites only the entries it read
   }
   __syncthreads();
+  if (a.hk) {   // sgp_batch_eval_vi_knots only: k_batch_knot_finish contracts H with the knots
+    double* hk = a.hk + (int64_t)prob * BR_T;
+    for (int e = tid; e < m * MM; e += 256)
+      if ((e & (MM - 1)) < m) hk[e] = Bm[e];
+  }
   double h = 0.0;
   for (int e = tid; e < m * MM; e += 256)
     if ((e & (MM - 1)) < m) h += Bm[e];
@@ -798,6 +806,229 @@ __global__ void __launch_bounds__(64) k_batch_pred_finish(BatchArgs a, BatchPred
     p.stats[4 * prob + tid] = rec_sum(p.rec + (int64_t)seg0 * BATCH_PREC + tid, BATCH_PREC, nseg);
 }
 
+// ------------------------------------------------------------------------------ knot gradient
+// sgp_batch_eval_vi_knots: delbo_dcov_par's knot branch
+// (R/vi_functions.R:425-593) with dsqexp_dx2 / dsqexp_dx2_ard
+// (R/covariance_function_derivatives.R:178-302) in adjoint form.  With W = G o K of pass 2 and
+// H = G22 o Kuu of the m x m stage,
+//   R_kc = sum_i W_ik (x_ic - u_kc),  Q_kc = 2 sum_l H_kl (u_lc - u_kc),
+//   dELBO / du_kc = (R_kc + Q_kc) / l_c^2, times the bounded transform's factor (quirk Q8).
+// The row pass forms T = W^T (X - o) and the column sums of W per segment, with o the problem's
+// first knot, so R_kc = T_kc - (u_kc - o_c) sum_i W_ik loses nothing to the size of the
+// coordinates.  k, G and W are rebuilt as pass2_body builds them; each wave then turns its
+// 16 x Mp tile of W through wave-private LDS into the A operand (knot on l & 15, rows
+// 4 q + (l >> 4)) and takes the staged x tile as the B operand (coordinate on l & 15), so the
+// MFMA contracts over the rows.
+constexpr int KXS = 68;   // the x tile's coordinate stride and the W tile's row stride (doubles)
+
+template <int NT, int NCB>
+__device__ __forceinline__ void knot_body(const BatchArgs& a, const double* __restrict__ P,
+                                          const double* __restrict__ pm, int64_t row0, int rows,
+                                          double* __restrict__ rec, double* xu_s, double* pp_s,
+                                          double* vec_s, double* xs, double* wt_s) {
+  constexpr int Mp = 16 * NT, SN = 4 * NT;
+  const int d = a.d, m = (int)P[BP_M];
+  const double sig2 = P[BP_SIG2], rz = 1.0 / P[BP_Z];
+  double* u_s = vec_s;             // [g][s]
+  double* rs = vec_s + MM;         // 64: r / z of this step's rows
+  double* rl_s = vec_s + 2 * MM;   // d
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, g = lane >> 4;
+  double* wt = wt_s + wv * 16 * KXS;   // the wave's own W tile [row][knot]
+
+  for (int q = tid; q < d * Mp; q += 256) {
+    const int c = q / Mp, j = q - c * Mp;
+    xu_s[(c * 4 + (j & 3)) * SN + (j >> 2)] = P[BP_U + c * MM + j];
+  }
+  for (int q = tid; q < Mp * Mp; q += 256) {
+    const int i = q / Mp, j = q - i * Mp;
+    pp_s[q] = (i < m && j < m) ? pm[i * MM + j] : 0.0;
+  }
+  for (int q = tid; q < Mp; q += 256) u_s[(q & 3) * SN + (q >> 2)] = q < m ? pm[BPM_U + q] : 0.0;
+  for (int q = tid; q < d; q += 256) rl_s[q] = P[BP_RL + q];
+  double ob[NCB];   // the offset of this lane's coordinate in block cb
+  bool cv[NCB];
+#pragma unroll
+  for (int cb = 0; cb < NCB; ++cb) {
+    cv[cb] = 16 * cb + r16 < d;
+    ob[cb] = cv[cb] ? P[BP_U + (16 * cb + r16) * MM] : 0.0;
+  }
+
+  d4 racc[NT][NCB];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) racc[t][cb] = d4{0.0, 0.0, 0.0, 0.0};
+  double cs[SN];
+#pragma unroll
+  for (int s = 0; s < SN; ++s) cs[s] = 0.0;
+
+  for (int step = 0; step * 64 < rows; ++step) {
+    __syncthreads();   // the staging above / the previous step's reads of xs, rs and wt
+    for (int q = tid; q < d * 64; q += 256) {
+      const int c = q >> 6, i = q & 63;
+      const int row = step * 64 + i;
+      xs[c * KXS + i] = row < rows ? a.X[(int64_t)c * a.ldx + row0 + row] : 0.0;
+    }
+    if (tid < 64) {
+      const int row = step * 64 + tid;
+      rs[tid] = row < rows ? (a.y[row0 + row] - a.mu[row0 + row]) * rz : 0.0;
+    }
+    __syncthreads();
+
+    const bool iv = step * 64 + wv * 16 + r16 < rows;
+    const double* xr = xs + wv * 16 + r16;
+    double e2[SN], kf[SN];
+#pragma unroll
+    for (int s = 0; s < SN; ++s) e2[s] = 0.0;
+    for (int c = 0; c < d; ++c) {
+      const double xc = xr[c * KXS], rl = rl_s[c];
+      const double* u = xu_s + (c * 4 + g) * SN;
+#pragma unroll
+      for (int s = 0; s < SN; ++s) {
+        const double t = (xc - u[s]) * rl;   // the raw difference first, as in pass 2
+        e2[s] = fma(t, t, e2[s]);
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < SN; ++s) {
+      const double v = sig2 * sgp_exp_nonpos(-0.5 * e2[s]);
+      kf[s] = (iv && 4 * s + g < m) ? v : 0.0;
+    }
+    d4 acc[NT];
+#pragma unroll
+    for (int cb = 0; cb < NT; ++cb) acc[cb] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < SN; ++s)
+#pragma unroll
+      for (int cb = 0; cb < NT; ++cb)
+        acc[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(pp_s[(4 * s + g) * Mp + 16 * cb + r16],
+                                                       kf[s], acc[cb], 0, 0, 0);
+    const double ri = rs[wv * 16 + r16];
+#pragma unroll
+    for (int cb = 0; cb < NT; ++cb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int s = 4 * cb + r;
+        const double gv = fma(ri, u_s[g * SN + s], acc[cb][r]);   // G = (r / z) u^T + K P'
+        const double w = gv * kf[s];
+        cs[s] += w;
+        wt[r16 * KXS + 4 * s + g] = w;
+      }
+    __syncthreads();   // the W tile is read across the wave's lanes
+    // T[16 t + i][16 cb + j] += sum over the wave's 16 rows: A[i][row] = W, B[row][j] = x - o
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      double bx[NCB];
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb)
+        bx[cb] = cv[cb] ? xs[(16 * cb + r16) * KXS + wv * 16 + 4 * q + g] - ob[cb] : 0.0;
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const double aw = wt[(4 * q + g) * KXS + 16 * t + r16];
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb)
+          racc[t][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(aw, bx[cb], racc[t][cb], 0, 0, 0);
+      }
+    }
+  }
+
+  // the four waves' partial T, added in wave order into LDS (over P', which is dead), and the
+  // column sums: over the lane's rows in step order, the 16 lanes by xor-shuffle, the waves in
+  // wave order
+  double* tb = pp_s;   // [knot][32]
+  double* cw = wt_s;   // [wave][64]
+  for (int w = 0; w < 4; ++w) {
+    __syncthreads();
+    if (wv == w) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            double* s = tb + (16 * t + 4 * r + g) * SGP_MAXD + 16 * cb + r16;
+            *s = w ? *s + racc[t][cb][r] : racc[t][cb][r];
+          }
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < SN; ++s) {
+    double v = cs[s];
+    v += __shfl_xor(v, 1, 64);
+    v += __shfl_xor(v, 2, 64);
+    v += __shfl_xor(v, 4, 64);
+    v += __shfl_xor(v, 8, 64);
+    if (r16 == 0) cw[wv * MM + 4 * s + g] = v;
+  }
+  __syncthreads();
+  for (int q = tid; q < m * d; q += 256) {
+    const int k = q / d, c = q - k * d;
+    rec[k * SGP_MAXD + c] = tb[k * SGP_MAXD + c];
+  }
+  if (tid < m) rec[BK_CS + tid] = ((cw[tid] + cw[MM + tid]) + cw[2 * MM + tid]) + cw[3 * MM + tid];
+}
+
+__global__ void __launch_bounds__(256) k_batch_knot_pass(BatchArgs a) {
+  __shared__ __attribute__((aligned(16))) double xu_s[SGP_MAXD * MM], pp_s[MM * MM];
+  __shared__ double vec_s[2 * MM + SGP_MAXD], xs[SGP_MAXD * KXS], wt_s[4 * 16 * KXS];
+  const int seg = blockIdx.x;
+  const int prob = a.seg_prob[seg];
+  const double* P = a.par + (int64_t)prob * a.pst;
+  if (P[BP_ACTIVE] == 0.0) return;
+  if (a.out[(int64_t)prob * BATCH_OUT + 1] != 0.0) return;   // the problem failed in k_batch_mm
+  const double* pm = a.pm + (int64_t)prob * BATCH_PM;
+  const int64_t row0 = a.seg_row0[seg];
+  const int rows = a.seg_rows[seg];
+  double* rec = a.rec3 + (int64_t)seg * BATCH_REC3;
+#define SGP_KNOT_CASE(NT)                                                             \
+  if (a.d > 16) knot_body<NT, 2>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, wt_s); \
+  else knot_body<NT, 1>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, wt_s);          \
+  break;
+  switch (((int)P[BP_M] + 15) >> 4) {
+    case 1: SGP_KNOT_CASE(1)
+    case 2: SGP_KNOT_CASE(2)
+    case 3: SGP_KNOT_CASE(3)
+    default: SGP_KNOT_CASE(4)
+  }
+#undef SGP_KNOT_CASE
+}
+
+// The segments' records in segment order, the K22 part from H and the knots, 1 / l_c^2 and the
+// chain factor of the bounded transform; problem b's m d values go out knot-major (quirk Q16) at
+// its offset in the packed result.
+__global__ void __launch_bounds__(256) k_batch_knot_finish(BatchArgs a) {
+  __shared__ double H[MM * MM], cs[MM];
+  const int prob = blockIdx.x, tid = threadIdx.x;
+  const double* P = a.par + (int64_t)prob * a.pst;
+  if (P[BP_ACTIVE] == 0.0) return;
+  if (a.out[(int64_t)prob * BATCH_OUT + 1] != 0.0) return;
+  const int d = a.d, m = (int)P[BP_M];
+  const int seg0 = (int)P[BP_SEG0], nseg = (int)P[BP_NSEG];
+  const double* rec = a.rec3 + (int64_t)seg0 * BATCH_REC3;
+  const double* hk = a.hk + (int64_t)prob * BR_T;
+  for (int e = tid; e < m * MM; e += 256)
+    if ((e & (MM - 1)) < m) H[e] = hk[e];
+  if (tid < m) cs[tid] = rec_sum(rec + BK_CS + tid, BATCH_REC3, nseg);
+  __syncthreads();
+  double* gk = a.gk + (int64_t)P[BP_GOFF];
+  const double* bnd = a.bnd ? a.bnd + (int64_t)prob * 2 * d : nullptr;   // [lower | upper], d each
+  for (int q = tid; q < m * d; q += 256) {
+    const int k = q / d, c = q - k * d;
+    const double* u = P + BP_U + c * MM;
+    const double ukc = u[k];
+    const double r = rec_sum(rec + k * SGP_MAXD + c, BATCH_REC3, nseg) - (ukc - u[0]) * cs[k];
+    double h = 0.0;
+    for (int l = 0; l < m; ++l) h = fma(H[k * MM + l], u[l] - ukc, h);
+    const double rl = P[BP_RL + c];
+    double v = (r + 2.0 * h) * (rl * rl);
+    if (bnd) {
+      const double lb = bnd[c], ub = bnd[d + c];
+      v *= (ub - lb) / ((ukc - lb) * (ub - ukc) + 1e-4);
+    }
+    gk[q] = v;
+  }
+}
+
 }  // namespace
 
 hipError_t launch_batch_eval(const BatchArgs& a, hipStream_t s, hipEvent_t* ev) {
@@ -849,5 +1080,19 @@ hipError_t launch_batch_predict(const BatchArgs& a, const BatchPredArgs& p, hipS
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (ev) e = hipEventRecord(ev[3], s);
+  return e;
+}
+
+hipError_t launch_batch_knots(const BatchArgs& a, hipStream_t s, hipEvent_t* ev) {
+  if (a.B < 1 || a.nseg < 1 || a.d < 1 || a.d > SGP_MAXD || !a.hk || !a.rec3 || !a.gk)
+    return hipErrorInvalidValue;
+  hipError_t e = hipSuccess;
+  if (ev && (e = hipEventRecord(ev[0], s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_batch_knot_pass, dim3((unsigned)a.nseg), dim3(256), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (ev && (e = hipEventRecord(ev[1], s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_batch_knot_finish, dim3((unsigned)a.B), dim3(256), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (ev) e = hipEventRecord(ev[2], s);
   return e;
 }

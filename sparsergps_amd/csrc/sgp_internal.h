@@ -611,6 +611,7 @@ hipError_t launch_rec_gather(const RecPass2& p2, const GatherSegs& g, double* ds
 // A problem's parameter block (doubles; integers are held exactly), stride 48 + 64 d
 enum {
   BP_M = 0, BP_ACTIVE, BP_SIG2, BP_TAU2, BP_Z, BP_DELTA, BP_NROW, BP_RDET, BP_SEG0, BP_NSEG,
+  BP_GOFF,                      // sgp_batch_eval_vi_knots: the problem's offset in the packed result
   BP_RL = 16,                   // 1 / l_c, d values ("sqexp": 1 / l in each)
   BP_U = 48                     // knots [c][64], zero beyond m
 };
@@ -622,6 +623,8 @@ constexpr int BATCH_PM = BPM_KD + SGP_BATCH_MMAX;   // P' (row stride 64) | u | 
 enum { BS_TRACE = 0, BS_TRBS, BS_ATA, BS_G22 = 4 }; // the m x m stage's scalars; G22 terms: P values
 constexpr int BATCH_SC = BS_G22 + SGP_MAXD + 4;
 constexpr int BATCH_OUT = SGP_MAXD + 8;  // obj | status | grad (P values)
+// the knot pass's record (sec. 0p): T = W^T (X - o) (m x d, row stride 32) | the column sums of W
+constexpr int BK_CS = SGP_BATCH_MMAX * SGP_MAXD, BATCH_REC3 = BK_CS + SGP_BATCH_MMAX;
 struct BatchArgs {
   const double *X, *y, *mu;     // the resident rows (X column-major, ld ldx)
   int64_t ldx;
@@ -634,11 +637,19 @@ struct BatchArgs {
   double *rec1, *rec2, *pm, *sc, *out;
   double* post;                 // per problem: Bm^-1 (row stride 64) | u | the parameter block
   int post_stride;
+  // sgp_batch_eval_vi_knots (sec. 0p); hk = nullptr in every other call
+  double* hk;                   // per problem: H = G22 o Kuu (row stride 64), stored by k_batch_mm
+  double* rec3;                 // nseg records of BATCH_REC3
+  const double* bnd;            // per problem d lower | d upper bounds, or nullptr (chain factor 1)
+  double* gk;                   // the packed knot gradients, problem b at BP_GOFF
 };
 // ev (or nullptr): 5 events recorded before pass 1, the m x m stage, pass 2, the finish and after
 hipError_t launch_batch_eval(const BatchArgs& a, hipStream_t s, hipEvent_t* ev);
 // res: per problem 64 * 64 + 64 doubles, u_var (row stride 64) | u_mean - muu
 hipError_t launch_batch_post(const BatchArgs& a, double* res, hipStream_t s);
+// after launch_batch_eval with a.hk set; ev (or nullptr): 3 events recorded before the knot pass,
+// the knot finish and after
+hipError_t launch_batch_knots(const BatchArgs& a, hipStream_t s, hipEvent_t* ev);
 
 // Batched held-out prediction and scoring (sgp_batch_predict) from the state
 // `post` holds.  A problem's work slot: T = Bm^-1 - K22^-1 (row stride 64) | c0 = (tau^2 +
