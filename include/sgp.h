@@ -507,6 +507,38 @@ int sgp_batch_eval_vi_knots(sgp_batch* b, int kernel, const double* theta, int64
                             int64_t ldg, int* status, const double* bounds /* NULL: raw */,
                             double* grad_knot);
 
+/* The batch's other Gaussian objective, FITC: what optimize_gp(vi = FALSE), the
+ * reference's own default, fits.  The arguments, their check (the same sgp_diag_batch_args, before
+ * the first device call), the limits, `active`, the status convention and the fixed-order rule are
+ * sgp_batch_eval_vi's; per problem the semantics are exactly sgp_eval_fitc's: K22 = Kuu + delta I,
+ * Z_i = sigma^2 + tau^2 + delta - k_i^T K22^-1 k_i (R/laplace_gradient_ascent.R:1238-1263),
+ * obj_fun_norm (R/laplace_approx_obj_funs.R:6-52) and dlogp_dcov_par
+ * (R/laplace_approx_gradient.R:720-971) with the gradient in log theta in sgp_num_params order,
+ * knots fixed, dK22 / dlog tau = 0 (l.899-902), the tau coincidence rule (quirk Q5: a row that
+ * equals a knot exactly gets dK12 / dlog tau = 2 tau^2), and SGP_FLAG_R_DET / SGP_FLAG_OBJ_ONLY
+ * with their sgp_eval_fitc meaning.  Five kernel launches evaluate the whole batch (three under
+ * SGP_FLAG_OBJ_ONLY, which skips the gradient's row pass and its m x m stage).
+ * status[b] = +k when the first non-positive leading minor, of order k, is in Sigma22 (K22) and
+ * -k when it is in K22 + K21 Z^-1 K12; obj and grad of that problem are NaN and the call returns
+ * SGP_OK.  A row whose Z_i is not positive and finite (the reference's log(Z) is NaN there; with
+ * an SPD K22 Z_i >= tau^2 + delta up to rounding, so only a negative delta reaches it) makes the
+ * problem's obj and grad NaN with status[b] = 0.  Either way the problem writes nothing to its
+ * posterior state.
+ * The posterior state of a successful problem is Bm^-1, u = Bm^-1 t (no 1 / z) and its
+ * parameters, where sgp_batch_eval_vi leaves them, with the objective recorded beside them:
+ * sgp_batch_posterior_u then gives laplace_gradient_ascent.R:1635-1655 (u_mean - muu = K22 u,
+ * u_var = K22 Bm^-1 K22) and sgp_batch_predict gives predict_laplace(family = "gaussian")
+ * (R/laplace_approx_prediction.R:3-123):
+ *   pred_mean_i = mu_i + k_i^T u
+ *   pred_var_i  = (sigma^2 + tau^2) + k_i^T (Bm^-1 - K22^-1) k_i        -- no delta, unlike predict_vi
+ * and the same nlp_i, for every problem whose last successful evaluation was FITC; one batch may
+ * hold problems of both kinds.  A problem's FITC result does not depend on whether earlier calls
+ * on the batch were VI or FITC, nor does a VI result. */
+int sgp_batch_eval_fitc(sgp_batch* b, int kernel, const double* theta, int64_t ldt,
+                        const double* U, const int64_t* uoff, const int64_t* m, double delta,
+                        unsigned flags, const unsigned char* active, double* obj, double* grad,
+                        int64_t ldg, int* status);
+
 /* Held-out prediction and scoring for a batch: predict_vi
  * (R/vi_functions.R:1222-1336) and my_nlp(family = "gaussian") (R/evaluation_functions.R:14-20,
  * with quirk Q23: pred_var + tau^2 as written) for every problem of the batch in three launches,
@@ -517,7 +549,10 @@ int sgp_batch_eval_vi_knots(sgp_batch* b, int kernel, const double* theta, int64
  *   pred_mean_i = mu_i + k_i^T u
  *   pred_var_i  = (tau^2 + sigma^2) + delta + k_i^T (Bm^-1 - K22^-1) k_i
  *   nlp_i       = -dnorm(y_i, pred_mean_i, sqrt(pred_var_i + tau^2), log = TRUE)
- * with the problem's own theta, knots, m and delta.
+ * with the problem's own theta, knots, m and delta.  For a problem whose last successful
+ * evaluation was sgp_batch_eval_fitc the same launches give predict_laplace(family = "gaussian"):
+ * u carries no 1 / z and the constant is sigma^2 + tau^2 without delta (see sgp_batch_eval_fitc
+ * above).
  *
  * set_test: Xt (ntest x d column-major, ld ldxt), yt (ntest values, or NULL: predict only) and
  * mut (ntest values) are uploaded once; problem b's test rows are [trow0[b], trow0[b] + tnrow[b]).

@@ -164,6 +164,12 @@ int sgp_diag_batch_knot_args(int d, int64_t B, unsigned flags, const unsigned ch
  * them from the next such call on.  sgp_diag_batch_timing covers that call's first four stages. */
 int sgp_diag_batch_knot_timing(struct sgp_batch* b, int enable, double* stage_ms);
 
+/* stage_ms (5 doubles, or NULL): the times by HIP events of K22's stage, the weighted first row
+ * pass, Bm's stage, the gradient's row pass and the G22 stage of the batch's last
+ * sgp_batch_eval_fitc (zeros when they were not recorded; the last two are zero under
+ * SGP_FLAG_OBJ_ONLY); enable != 0 records them from the next such call on. */
+int sgp_diag_batch_fitc_timing(struct sgp_batch* b, int enable, double* stage_ms);
+
 /* Host only: the argument checks of sgp_batch_set_test (stage 0: d, B and the arguments Xt ..
  * tnrow) and of sgp_batch_predict (stage 1: B and the arguments from have_test on) -- the very
  * function both run before their first device call.  have_test / have_yt: whether set_test was

@@ -169,6 +169,11 @@ PROTOTYPES = {
     "sgp_diag_batch_knot_args": (C.c_int, [C.c_int, C.c_int64, C.c_uint, c_ubyte_p, c_double_p,
                                            c_double_p]),
     "sgp_diag_batch_knot_timing": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    # the batch's FITC objective: sgp_batch_eval_vi's arguments
+    "sgp_batch_eval_fitc": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_int64, c_double_p,
+                                      c_int64_p, c_int64_p, C.c_double, C.c_uint, c_ubyte_p,
+                                      c_double_p, c_double_p, C.c_int64, c_int_p]),
+    "sgp_diag_batch_fitc_timing": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
     # held-out prediction and scoring for a batch (Xt, ntest, ldxt, yt, mut, trow0, tnrow)
     "sgp_batch_set_test": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, c_double_p,
                                      c_double_p, c_int64_p, c_int64_p]),

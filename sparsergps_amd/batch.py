@@ -1,4 +1,5 @@
-"""Batched small-knot VI fits: many independent problems per launch.
+"""Batched small-knot VI and FITC fits: many independent problems per launch (DESIGN.md sec. 0n,
+0q).
 
   SparseGPBatch                B problems (row ranges of one resident X / y / mu), each with its own
                                theta and at most 64 knots: sgp_batch_* of include/sgp.h
@@ -15,6 +16,10 @@
                                on the device
   cross_validate_gp            k-fold cross-validation: the folds fitted in lockstep and scored on
                                one batch
+  SparseGPBatch.eval_fitc      the other Gaussian objective (obj_fun_norm / dlogp_dcov_par;
+                               DESIGN.md sec. 0q), which norm_grad_ascent_batch ascends on and
+                               vi = False of optimize_gp_batch / cross_validate_gp fits; predict and
+                               score then give predict_laplace(family = "gaussian")
 
 Per problem the semantics are the single fit's (drivers._ascent, the knots fixed or moved with
 theta: optimize_gp's xu_opt = "fixed" / "simultaneous", R/optimize_gp.R:299-333, 378-412); a problem
@@ -121,9 +126,9 @@ class SparseGPBatch:
         self._eval(cov_fun, theta, xus, delta, flags, active, obj, grad, status)
 
     def _eval(self, cov_fun, theta, xus, delta, flags, active, obj, grad, status, knots=False,
-              bounds=None):
-        """sgp_batch_eval_vi, or with knots sgp_batch_eval_vi_knots (bounds: B x 2d or None);
-        returns (grad_knot packed like U, uoff, m) with knots."""
+              bounds=None, fitc=False):
+        """sgp_batch_eval_vi, with knots sgp_batch_eval_vi_knots (bounds: B x 2d or None), with
+        fitc sgp_batch_eval_fitc; returns (grad_knot packed like U, uoff, m) with knots."""
         self._need()
         theta = np.ascontiguousarray(theta, dtype=np.float64)
         on = [active is None or bool(active[b]) for b in range(self.B)]
@@ -148,11 +153,13 @@ class SparseGPBatch:
             bd = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.float64)
             st = self._lib.sgp_batch_eval_vi_knots(*args, None if bd is None else _lib.dptr(bd),
                                                    _lib.dptr(gk))
+        elif fitc:
+            st = self._lib.sgp_batch_eval_fitc(*args)
         else:
             st = self._lib.sgp_batch_eval_vi(*args)
         _lib.check(st)
         for b in range(self.B):
-            if on[b] and status[b] == 0:
+            if on[b] and status[b] == 0 and not (fitc and np.isnan(obj[b])):
                 self._state[b] = int(m[b])
         return gk, uoff, m
 
@@ -163,6 +170,11 @@ class SparseGPBatch:
         OrderedDicts in each cov_par's key order (None for inactive problems and with
         obj_only); a problem with status != 0 has NaN obj and grad (chol()'s leading-minor order:
         > 0 for Sigma22, < 0 for Sigma22 + t(Sigma12) %*% ZSig12).  Inactive slots are NaN / 0."""
+        return self._eval_pars(self.eval_raw, cov_pars, cov_fun, xus, delta, active, obj_only,
+                               r_det)
+
+    def _eval_pars(self, run, cov_pars, cov_fun, xus, delta, active, obj_only, r_det):
+        """eval_vi / eval_fitc on run = eval_raw / eval_fitc_raw."""
         P = (self.d if cov_fun == "ard" else 1) + 2
         theta = np.ones((self.B, P))
         on = [active is None or bool(active[b]) for b in range(self.B)]
@@ -173,8 +185,32 @@ class SparseGPBatch:
         g = None if obj_only else np.full((self.B, P), np.nan)
         status = np.zeros(self.B, dtype=np.int32)
         flags = (_lib.SGP_FLAG_OBJ_ONLY if obj_only else 0) | (_lib.SGP_FLAG_R_DET if r_det else 0)
-        self.eval_raw(cov_fun, theta, xus, delta, flags, active, obj, g, status)
+        run(cov_fun, theta, xus, delta, flags, active, obj, g, status)
         return obj, self._named(cov_pars, cov_fun, g, on), status
+
+    def eval_fitc_raw(self, cov_fun, theta, xus, delta, flags, active, obj, grad, status):
+        """sgp_batch_eval_fitc on caller-owned arrays, as eval_raw."""
+        self._eval(cov_fun, theta, xus, delta, flags, active, obj, grad, status, fitc=True)
+
+    def eval_fitc(self, cov_pars, cov_fun, xus, delta=1e-6, active=None, obj_only=False,
+                  r_det=False):
+        """One FITC evaluation of the batch (sgp_batch_eval_fitc: obj_fun_norm and
+        dlogp_dcov_par per problem, as SparseGPContext.eval_fitc gives them for one).  The
+        arguments and the return value are eval_vi's: (obj[B], grad, status[B]); status < 0 names
+        Sigma22 + t(Sigma12) %*% ZSig12.  posterior_u, predict and score afterwards are
+        laplace_gradient_ascent.R:1635-1655 and predict_laplace(family = "gaussian") for the
+        problems this call evaluated."""
+        return self._eval_pars(self.eval_fitc_raw, cov_pars, cov_fun, xus, delta, active,
+                               obj_only, r_det)
+
+    def fitc_stage_ms(self, enable=True):
+        """HIP-event times (ms) of the last eval_fitc's five stages (K22's stage, the weighted
+        pass 1, Bm's stage, the gradient pass, the G22 stage); records from the next one on."""
+        self._need()
+        out = np.zeros(5)
+        _lib.check(self._lib.sgp_diag_batch_fitc_timing(self._h, int(bool(enable)),
+                                                        _lib.dptr(out)))
+        return out
 
     def _named(self, cov_pars, cov_fun, g, on):
         names = param_names(cov_fun, self.d)
@@ -346,8 +382,9 @@ class SparseGPBatch:
         return test, pm, pv, nlp, stats
 
     def predict(self, active=None):
-        """predict_vi for every active problem on its test rows, from the posterior of its last
-        successful evaluation: a list of {"pred_mean": (n_b, 1), "pred_var": (n_b,)}, None for
+        """predict_vi (predict_laplace(family = "gaussian") where that evaluation was eval_fitc)
+        for every active problem on its test rows, from the posterior of its last successful
+        evaluation: a list of {"pred_mean": (n_b, 1), "pred_var": (n_b,)}, None for
         inactive problems."""
         (_, nr, off, _), pm, pv, _, _ = self._run_predict(active, False)
         return [None if active is not None and not active[b] else
@@ -355,7 +392,8 @@ class SparseGPBatch:
                  "pred_var": pv[off[b]:off[b] + nr[b]].copy()} for b in range(self.B)]
 
     def score(self, active=None):
-        """score_gp(vi = True) for every active problem on its test rows: a list of {"pred",
+        """score_gp(vi = True) (vi = False after eval_fitc) for every active problem on its test
+        rows: a list of {"pred",
         "nlp", "median_nlp", "mean_nlp", "rmse", "srmse", "n_nan"} dicts (None for inactive
         problems), the nlp with each problem's own tau."""
         self._need()
@@ -463,6 +501,36 @@ def norm_grad_ascent_vi_batch(cov_par_starts, cov_fun, xus, batch, muus=None, op
             batch.close()
 
 
+_ERR_FITC_KNOTS = ('xu_opt = "simultaneous" with vi = False: FITC batches have no knot gradient '
+                   'yet; use xu_opt = "fixed", vi = True, or optimize_gp')
+
+
+def norm_grad_ascent_batch(cov_par_starts, cov_fun, xus, batch, muus=None, opt=None,
+                           dcov_fun_dknot=None, xu_opt="fixed", knot_opt=None):
+    """B norm_grad_ascent runs (R/laplace_gradient_ascent.R:1111-1693, the FITC objective) in
+    lockstep on one batch: every iteration is one batch.eval_fitc call over the problems still
+    running.  The arguments and the return value are norm_grad_ascent_vi_batch's, the dicts being
+    those norm_grad_ascent returns (u_mean / u_var from laplace_gradient_ascent.R:1635-1655);
+    status < 0 of a problem that is not positive definite names
+    Sigma22 + t(Sigma12) %*% ZSig12.  xu_opt = "simultaneous" is refused: FITC batches have no
+    knot gradient yet."""
+    if not (dcov_fun_dknot is None or dcov_fun_dknot is False or
+            (isinstance(dcov_fun_dknot, float) and np.isnan(dcov_fun_dknot))):
+        raise ValueError("norm_grad_ascent_batch: knot gradients are not supported "
+                         "(dcov_fun_dknot must be None)")
+    if _xu_opt(xu_opt, "norm_grad_ascent_batch"):
+        raise ValueError("norm_grad_ascent_batch: " + _ERR_FITC_KNOTS)
+    o = _opts(opt)
+    own = not hasattr(batch, "eval_fitc")
+    if own:
+        batch = SparseGPBatch.from_problems(batch)
+    try:
+        return _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o, objective="fitc")
+    finally:
+        if own:
+            batch.close()
+
+
 def _bounded(t, bounds):
     """drivers._bounded in the reference's order of operations, a product with the reciprocal
     (trans_fun, covariance_function_derivatives.R:191-197): a last-bit difference in a knot shows
@@ -490,7 +558,13 @@ def _knot_keep(knot_opt, B, ms, d):
     return out
 
 
-def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o, simul=False, knot_opt=None):
+def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o, simul=False, knot_opt=None,
+              objective="vi"):
+    """objective: "vi" (batch.eval_vi / eval_vi_knots) or "fitc" (batch.eval_fitc, knots fixed)."""
+    if objective not in ("vi", "fitc"):
+        raise ValueError(f'_lockstep: objective must be "vi" or "fitc", not {objective!r}')
+    if simul and objective == "fitc":
+        raise ValueError(_ERR_FITC_KNOTS)
     B = batch.B
     if len(cov_par_starts) != B or len(xus) != B:
         raise ValueError(f"norm_grad_ascent_vi_batch: {B} problems, {len(cov_par_starts)} "
@@ -529,6 +603,8 @@ def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o, simul=False, knot_op
         if simul:
             ob, gr, kg, st = batch.eval_vi_knots(pars, cov_fun, xus, o["delta"], active=active,
                                                  bounds=bounds)
+        elif objective == "fitc":
+            ob, gr, st = batch.eval_fitc(pars, cov_fun, xus, o["delta"], active=active)
         else:
             ob, gr, st = batch.eval_vi(pars, cov_fun, xus, o["delta"], active=active)
         for b in range(B):
@@ -640,15 +716,21 @@ _ERR_Q10 = ('xu_opt = "simultaneous" passes cov_fun = "sqexp" to the driver '
             '(R/optimize_gp.R:320, 399), which cannot take an "ard" fit\'s cov_par; use "fixed"')
 
 
-def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None, xu_opt="fixed"):
+def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None, xu_opt="fixed",
+                      vi=True):
     """optimize_gp(y, xy, cov_fun, cov_par_start, mu, family = "gaussian", sparse = TRUE,
-    xu_opt, xu, muu, vi = TRUE, opt) for each (xy, y, mu) of `problems`, fitted in lockstep on
-    one batch.  xu_opt: "fixed" or "simultaneous" (all knots move, R/optimize_gp.R:396-412; with
+    xu_opt, xu, muu, vi, opt) for each (xy, y, mu) of `problems`, fitted in lockstep on
+    one batch.  vi: True (the default here, as before) for the Titsias ELBO; False for FITC, the
+    fit of optimize_gp(vi = FALSE) -- the reference's own default is vi = FALSE -- whose models
+    predict_gp(mod, ..., vi=False), predictor_gp and score_gp(vi=False) take; with vi = False
+    xu_opt = "simultaneous" raises a ValueError (FITC batches have no knot gradient yet).  xu_opt: "fixed" or "simultaneous" (all knots move, R/optimize_gp.R:396-412; with
     cov_fun = "ard" optimize_gp's quirk-Q10 ValueError); "oat" and "random" are refused.  cov_par_start, xu and muu: one value for all problems or a list with
     one per problem.  Returns a list of optimize_gp's {"results", "sparse", "family", "delta",
     "xu_init"} dicts (or its error strings), which predict_gp, predictor_gp and score_gp take."""
     from .optimize import ERR_COV, ERR_GA, ERR_MAXKNOT, OPT_MASTER
     simul = _xu_opt(xu_opt, "optimize_gp_batch")
+    if simul and not vi:
+        raise ValueError("optimize_gp_batch: " + _ERR_FITC_KNOTS)
     B = len(problems)
     o = {k: (dict(v) if isinstance(v, dict) else v) for k, v in OPT_MASTER.items()}
     for k, v in (opt or {}).items():
@@ -671,9 +753,9 @@ def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None, 
         u, mb = _knots_and_muu(xus[b], muus[b])
         keep.append((b, (xy, prob[1], prob[2] if len(prob) > 2 else None), u, mb))
     if keep:
-        res = norm_grad_ascent_vi_batch([starts[b] for b, *_ in keep], cov_fun,
-                                        [u for _, _, u, _ in keep], [p for _, p, _, _ in keep],
-                                        [mb for *_, mb in keep], o, xu_opt=xu_opt)
+        driver = norm_grad_ascent_vi_batch if vi else norm_grad_ascent_batch
+        res = driver([starts[b] for b, *_ in keep], cov_fun, [u for _, _, u, _ in keep],
+                     [p for _, p, _, _ in keep], [mb for *_, mb in keep], o, xu_opt=xu_opt)
         for (b, _, u, _), r in zip(keep, res):
             out[b] = {"results": r, "sparse": True, "family": "gaussian", "delta": o["delta"],
                       "xu_init": u}
@@ -681,10 +763,13 @@ def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None, 
 
 
 def cross_validate_gp(y, xy, cov_fun, cov_par_start, xu, folds=5, mu=None, muu=None, opt=None,
-                      rng=None, xu_opt="fixed"):
-    """k-fold cross-validation of optimize_gp(family = "gaussian", sparse = TRUE, vi = TRUE,
+                      rng=None, xu_opt="fixed", vi=True):
+    """k-fold cross-validation of optimize_gp(family = "gaussian", sparse = TRUE, vi,
     xu_opt): every fold's fit runs in lockstep on one batch and every fold's held-out rows are
-    scored on it (SparseGPBatch.score), without the posteriors leaving the device.  xu_opt is
+    scored on it (SparseGPBatch.score), without the posteriors leaving the device.  vi: True (the
+    default here, as before) for the Titsias ELBO and score_gp(vi = True)'s figures; False for
+    FITC -- the reference's own default is vi = FALSE -- and score_gp(vi = False)'s figures, with
+    xu_opt = "simultaneous" then refused by a ValueError (FITC batches have no knot gradient yet).  xu_opt is
     optimize_gp_batch's: "fixed", or "simultaneous" for folds whose knots move (each on
     knot_bounds of its own training rows); the scores then use the moved knots.
 
@@ -701,6 +786,8 @@ def cross_validate_gp(y, xy, cov_fun, cov_par_start, xu, folds=5, mu=None, muu=N
     rows), "fold_id"}; the pooled figures cover the folds that were scored."""
     from .optimize import ERR_COV, ERR_GA, ERR_MAXKNOT, OPT_MASTER
     simul = _xu_opt(xu_opt, "cross_validate_gp")
+    if simul and not vi:
+        raise ValueError("cross_validate_gp: " + _ERR_FITC_KNOTS)
     y = np.asarray(y, dtype=np.float64).reshape(-1)
     n = y.size
     xy = _mat(xy, n)
@@ -747,7 +834,8 @@ def cross_validate_gp(y, xy, cov_fun, cov_par_start, xu, folds=5, mu=None, muu=N
         mbs.append(mb)
     batch = SparseGPBatch.from_problems(problems)
     try:
-        res = norm_grad_ascent_vi_batch(starts, cov_fun, us, batch, mbs, o, xu_opt=xu_opt)
+        driver = norm_grad_ascent_vi_batch if vi else norm_grad_ascent_batch
+        res = driver(starts, cov_fun, us, batch, mbs, o, xu_opt=xu_opt)
         ok = np.array(["error" not in r for r in res], dtype=np.uint8)
         scores = [None] * B
         if ok.any():

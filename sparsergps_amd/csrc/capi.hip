@@ -5260,6 +5260,11 @@ struct sgp_batch {
   // sgp_batch_eval_vi_knots (sec. 0p): par and h_par end in B bound blocks of 2 d, out and h_out
   // in the packed knot gradients (up to 64 d per problem), so a call is one copy each way
   double *hk = nullptr, *rec3 = nullptr;
+  // sgp_batch_eval_fitc (sec. 0q): the problems' work slots and the gradient pass's records
+  double *fw = nullptr, *rec4 = nullptr;
+  hipEvent_t fev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  float fstage_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  bool ftiming = false;
   hipEvent_t kev[3] = {nullptr, nullptr, nullptr};
   float kstage_ms[2] = {0.f, 0.f};
   bool ktiming = false;
@@ -5522,8 +5527,10 @@ void batch_free(sgp_batch* b) {
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : b->kev)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : b->fev)
+    if (e) (void)hipEventDestroy(e);
   for (double* p : {b->X, b->y, b->mu, b->par, b->rec1, b->rec2, b->pm, b->sc, b->out, b->post,
-                    b->res, b->hk, b->rec3})
+                    b->res, b->hk, b->rec3, b->fw, b->rec4})
     if (p) (void)hipFree(p);
   if (b->seg_prob) (void)hipFree(b->seg_prob);
   if (b->seg_rows) (void)hipFree(b->seg_rows);
@@ -5545,6 +5552,7 @@ BatchArgs batch_args(const sgp_batch* b, int ard, int obj_only) {
   a.rec1 = b->rec1; a.rec2 = b->rec2; a.pm = b->pm; a.sc = b->sc; a.out = b->out;
   a.post = b->post; a.post_stride = b->post_stride;
   a.hk = nullptr; a.rec3 = nullptr; a.bnd = nullptr; a.gk = nullptr;
+  a.fw = b->fw; a.rec4 = b->rec4;
   return a;
 }
 
@@ -5568,6 +5576,7 @@ int batch_create_impl(sgp_batch* b, const double* X, int64_t ldx, const double* 
   HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
   for (hipEvent_t& e : b->ev) HIPCHK(hipEventCreate(&e));
   for (hipEvent_t& e : b->kev) HIPCHK(hipEventCreate(&e));
+  for (hipEvent_t& e : b->fev) HIPCHK(hipEventCreate(&e));
   const int64_t gcap = B * SGP_BATCH_MMAX * d;   // the packed knot gradients at their largest
   HIPCHK(hipMalloc(&b->X, sizeof(double) * n * d));
   HIPCHK(hipMalloc(&b->y, sizeof(double) * n));
@@ -5580,6 +5589,8 @@ int batch_create_impl(sgp_batch* b, const double* X, int64_t ldx, const double* 
   HIPCHK(hipMalloc(&b->out, sizeof(double) * (B * BATCH_OUT + gcap)));
   HIPCHK(hipMalloc(&b->hk, sizeof(double) * B * BR_T));
   HIPCHK(hipMalloc(&b->rec3, sizeof(double) * b->nseg * BATCH_REC3));
+  HIPCHK(hipMalloc(&b->fw, sizeof(double) * B * BATCH_FW));
+  HIPCHK(hipMalloc(&b->rec4, sizeof(double) * b->nseg * BATCH_REC4));
   HIPCHK(hipMalloc(&b->post, sizeof(double) * B * b->post_stride));
   HIPCHK(hipMalloc(&b->res, sizeof(double) * B * (BR_T + SGP_BATCH_MMAX)));
   HIPCHK(hipMalloc(&b->seg_prob, sizeof(int) * b->nseg));
@@ -5712,8 +5723,9 @@ int sgp_batch_set_data(sgp_batch* b, const double* y, const double* mu) {
 namespace {
 
 // sgp_batch_eval_vi (grad_knot = nullptr) and sgp_batch_eval_vi_knots after their checks: the
-// same four launches on the same arguments, and with grad_knot the two knot launches behind them
-int batch_eval_impl(sgp_batch* b, int kernel, const double* theta, int64_t ldt, const double* U,
+// same four launches on the same arguments, and with grad_knot the two knot launches behind them;
+// sgp_batch_eval_fitc (fitc = 1, grad_knot = nullptr): its five launches on the same arguments
+int batch_eval_impl(sgp_batch* b, int fitc, int kernel, const double* theta, int64_t ldt, const double* U,
                     const int64_t* uoff, const int64_t* m, double delta, unsigned flags,
                     const unsigned char* active, double* obj, double* grad, int64_t ldg,
                     int* status, const double* bounds, double* grad_knot) {
@@ -5739,6 +5751,7 @@ int batch_eval_impl(sgp_batch* b, int kernel, const double* theta, int64_t ldt, 
     h[BP_SEG0] = (double)b->seg0[(size_t)p];
     h[BP_NSEG] = (double)b->nsegs[(size_t)p];
     h[BP_GOFF] = (double)gtot;
+    h[BP_OBJ] = fitc ? 1.0 : 0.0;
     gtot += m[p] * d;
     for (int c = 0; c < d; ++c) h[BP_RL + c] = 1.0 / th[1 + (ard ? c : 0)];
     const double* u = U + uoff[p];
@@ -5760,14 +5773,18 @@ int batch_eval_impl(sgp_batch* b, int kernel, const double* theta, int64_t ldt, 
     a.bnd = bounds ? b->par + npar : nullptr;
     a.gk = b->out + b->B * BATCH_OUT;
   }
-  HIPCHK(launch_batch_eval(a, b->stream, b->timing ? b->ev : nullptr));
+  if (fitc) HIPCHK(launch_batch_eval_fitc(a, b->stream, b->ftiming ? b->fev : nullptr));
+  else HIPCHK(launch_batch_eval(a, b->stream, b->timing ? b->ev : nullptr));
   if (grad_knot) HIPCHK(launch_batch_knots(a, b->stream, b->ktiming ? b->kev : nullptr));
   HIPCHK(hipMemcpyAsync(b->h_out, b->out,
                         sizeof(double) * (b->B * BATCH_OUT + (grad_knot ? gtot : 0)),
                         hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
-  if (b->timing)
+  if (!fitc && b->timing)
     for (int q = 0; q < 4; ++q) HIPCHK(hipEventElapsedTime(&b->stage_ms[q], b->ev[q], b->ev[q + 1]));
+  if (fitc && b->ftiming)
+    for (int q = 0; q < 5; ++q)
+      HIPCHK(hipEventElapsedTime(&b->fstage_ms[q], b->fev[q], b->fev[q + 1]));
   if (grad_knot && b->ktiming)
     for (int q = 0; q < 2; ++q)
       HIPCHK(hipEventElapsedTime(&b->kstage_ms[q], b->kev[q], b->kev[q + 1]));
@@ -5792,6 +5809,11 @@ int batch_eval_impl(sgp_batch* b, int kernel, const double* theta, int64_t ldt, 
       continue;
     }
     obj[p] = o[0];
+    if (fitc && std::isnan(o[0])) {   // some Z_i is not positive and finite: no posterior
+      if (grad)
+        for (int q = 0; q < P; ++q) grad[p * ldg + q] = NAN;
+      continue;
+    }
     if (!obj_only)
       for (int q = 0; q < P; ++q) grad[p * ldg + q] = o[2 + q];
     if (grad_knot) {
@@ -5816,8 +5838,31 @@ int sgp_batch_eval_vi(sgp_batch* b, int kernel, const double* theta, int64_t ldt
   const int cst = batch_check_eval(b->d, b->B, kernel, theta, ldt, U, uoff, m, delta, flags,
                                    active, obj, grad, ldg, status);
   if (cst != SGP_OK) return cst;
-  return batch_eval_impl(b, kernel, theta, ldt, U, uoff, m, delta, flags, active, obj, grad, ldg,
-                         status, nullptr, nullptr);
+  return batch_eval_impl(b, 0, kernel, theta, ldt, U, uoff, m, delta, flags, active, obj, grad,
+                         ldg, status, nullptr, nullptr);
+}
+
+int sgp_batch_eval_fitc(sgp_batch* b, int kernel, const double* theta, int64_t ldt,
+                        const double* U, const int64_t* uoff, const int64_t* m, double delta,
+                        unsigned flags, const unsigned char* active, double* obj, double* grad,
+                        int64_t ldg, int* status) {
+  if (!b) { set_err("sgp_batch_eval_fitc: the sgp_batch is NULL"); return SGP_EINVAL; }
+  const int cst = batch_check_eval(b->d, b->B, kernel, theta, ldt, U, uoff, m, delta, flags,
+                                   active, obj, grad, ldg, status);
+  if (cst != SGP_OK) return cst;
+  return batch_eval_impl(b, 1, kernel, theta, ldt, U, uoff, m, delta, flags, active, obj, grad,
+                         ldg, status, nullptr, nullptr);
+}
+
+/* stage_ms (5 doubles, or NULL): the HIP-event times of K22's stage, the weighted pass 1, Bm's
+ * stage, the gradient pass and the G22 stage of the last sgp_batch_eval_fitc; enable != 0 records
+ * them from the next such call on. */
+int sgp_diag_batch_fitc_timing(sgp_batch* b, int enable, double* stage_ms) {
+  if (!b) { set_err("sgp_diag_batch_fitc_timing: the sgp_batch is NULL"); return SGP_EINVAL; }
+  if (stage_ms)
+    for (int q = 0; q < 5; ++q) stage_ms[q] = b->ftiming ? (double)b->fstage_ms[q] : 0.0;
+  b->ftiming = enable != 0;
+  return SGP_OK;
 }
 
 int sgp_diag_batch_knot_args(int d, int64_t B, unsigned flags, const unsigned char* active,
@@ -5835,8 +5880,8 @@ int sgp_batch_eval_vi_knots(sgp_batch* b, int kernel, const double* theta, int64
   cst = batch_check_eval(b->d, b->B, kernel, theta, ldt, U, uoff, m, delta, flags, active, obj,
                          grad, ldg, status);
   if (cst != SGP_OK) return cst;
-  return batch_eval_impl(b, kernel, theta, ldt, U, uoff, m, delta, flags, active, obj, grad, ldg,
-                         status, bounds, grad_knot);
+  return batch_eval_impl(b, 0, kernel, theta, ldt, U, uoff, m, delta, flags, active, obj, grad,
+                         ldg, status, bounds, grad_knot);
 }
 
 /* stage_ms (2 doubles, or NULL): the HIP-event times of the knot pass and the knot finish of the

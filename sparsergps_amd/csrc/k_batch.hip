@@ -23,42 +23,17 @@
 // The knot gradient (sgp_batch_eval_vi_knots) at the end of the file:
 // k_batch_knot_pass per segment and k_batch_knot_finish per problem, after the evaluation's four
 // launches, under the same rules again.
+// The FITC evaluation of the same batch (sgp_batch_eval_fitc) is
+// k_batch_fitc.hip; it leaves Bm^-1, u and the parameter block in `post` as k_batch_mm does, with
+// the objective at BP_OBJ, so k_batch_post serves it unchanged and k_batch_pred_mm only chooses
+// predict_laplace's constant (no delta) for it.  sgp_batch_dev.h holds the helpers both files use.
 #include <math.h>
 
 #include "sgp_internal.h"
+#include "sgp_batch_dev.h"
 #include "sgp_quad.h"
 
 namespace {
-
-constexpr int MM = SGP_BATCH_MMAX;   // 64: the LDS matrices' row stride
-
-// sum of v over the 256 threads in a fixed tree order; red: 256 doubles
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (tid < st) red[tid] += red[tid + st];
-    __syncthreads();
-  }
-  return red[0];
-}
-
-// sum of rec[q * stride], q = 0 .. n - 1, in that order; the loads go out eight at a time
-__device__ __forceinline__ double rec_sum(const double* __restrict__ rec, int64_t stride, int n) {
-  double s = 0.0;
-  int q = 0;
-  for (; q + 8 <= n; q += 8) {
-    double v[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = rec[(q + k) * stride];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += v[k];
-  }
-  for (; q < n; ++q) s += rec[q * stride];
-  return s;
-}
 
 // ------------------------------------------------------------------------------ row pass 1
 template <int NT>
@@ -202,52 +177,6 @@ __global__ void __launch_bounds__(256) k_batch_pass1(BatchArgs a) {
 }
 
 // ------------------------------------------------------------------------------ m x m stage
-// The sweep operator on the leading m x m of A (row stride 64, in LDS): after the m sweeps A holds
-// -A^-1.  On an SPD matrix the pivot of sweep k is the ratio of the leading minors of order k + 1
-// and k (the square of Cholesky's k-th diagonal), so the first pivot that is not positive gives
-// chol()'s "leading minor of order k + 1".  Returns 0 or that order; *ld = the log-determinant.
-__device__ int sweep_spd(double* A, int m, double* ck, double* ld) {
-  const int tid = threadIdx.x;
-  double l = 0.0;
-  for (int k = 0; k < m; ++k) {
-    __syncthreads();
-    const double dk = A[k * MM + k];
-    if (!(dk > 0.0)) return k + 1;
-    l += log(dk);
-    if (tid < m) ck[tid] = A[tid * MM + k];   // = row k: A stays symmetric
-    __syncthreads();
-    const double rd = 1.0 / dk;
-    for (int e = tid; e < m * MM; e += 256) {
-      const int i = e >> 6, j = e & (MM - 1);
-      if (j >= m) continue;
-      double v;
-      if (i == k) v = j == k ? -rd : ck[j] * rd;
-      else if (j == k) v = ck[i] * rd;
-      else v = A[i * MM + j] - ck[i] * (ck[j] * rd);
-      A[i * MM + j] = v;
-    }
-  }
-  __syncthreads();
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    A[i * MM + j] = -A[i * MM + j];
-  }
-  __syncthreads();
-  *ld = l;
-  return 0;
-}
-
-// (U_i - U_j) scaled, squared and summed: the exponent's -2 x
-__device__ __forceinline__ double knot_dist2(const double* __restrict__ P, int d, int i, int j) {
-  double s = 0.0;
-  for (int c = 0; c < d; ++c) {
-    const double t = (P[BP_U + c * MM + i] - P[BP_U + c * MM + j]) * P[BP_RL + c];
-    s = fma(t, t, s);
-  }
-  return s;
-}
-
 __global__ void __launch_bounds__(256) k_batch_mm(BatchArgs a) {
   __shared__ __attribute__((aligned(16))) double A[MM * MM], Bm[MM * MM], S[MM * MM], T[MM * MM];
   __shared__ double t_s[MM], u_s[MM], ck[MM], red[256];
@@ -645,7 +574,9 @@ __global__ void __launch_bounds__(256) k_batch_pred_mm(BatchArgs a, BatchPredArg
   double ld22 = 0.0;
   const int st = sweep_spd(A, m, ck, &ld22);
   double* w = p.pw + (int64_t)prob * BATCH_PW;
-  if (tid == 0) w[BPW_C0] = st ? NAN : (tau2 + sig2) + delta;
+  // predict_laplace's constant has no delta (laplace_approx_prediction.R:3-123; sec. 0q)
+  if (tid == 0)
+    w[BPW_C0] = st ? NAN : (P[BP_OBJ] != 0.0 ? tau2 + sig2 : (tau2 + sig2) + delta);
   if (st) return;
   for (int e = tid; e < m * MM; e += 256) {
     const int i = e >> 6, j = e & (MM - 1);

@@ -612,6 +612,7 @@ hipError_t launch_rec_gather(const RecPass2& p2, const GatherSegs& g, double* ds
 enum {
   BP_M = 0, BP_ACTIVE, BP_SIG2, BP_TAU2, BP_Z, BP_DELTA, BP_NROW, BP_RDET, BP_SEG0, BP_NSEG,
   BP_GOFF,                      // sgp_batch_eval_vi_knots: the problem's offset in the packed result
+  BP_OBJ,                       // the objective the evaluation ran: 0 Titsias VI, 1 FITC (sec. 0q)
   BP_RL = 16,                   // 1 / l_c, d values ("sqexp": 1 / l in each)
   BP_U = 48                     // knots [c][64], zero beyond m
 };
@@ -625,6 +626,15 @@ constexpr int BATCH_SC = BS_G22 + SGP_MAXD + 4;
 constexpr int BATCH_OUT = SGP_MAXD + 8;  // obj | status | grad (P values)
 // the knot pass's record (sec. 0p): T = W^T (X - o) (m x d, row stride 32) | the column sums of W
 constexpr int BK_CS = SGP_BATCH_MMAX * SGP_MAXD, BATCH_REC3 = BK_CS + SGP_BATCH_MMAX;
+// Batched FITC (sgp_batch_eval_fitc; k_batch_fitc.hip).  Its first row pass
+// writes pass 1's record with sum w r^2 at BR_RR, sum log Z at BR_RR + 1 and the count of rows
+// whose Z is not positive and finite at BR_RR + 2.  A problem's work slot: K22^-1 | Bm^-1 (row
+// stride 64 each) | u | log|K22|, the bad-Z flag.  The gradient pass's record: S_omega (row
+// stride 64) | sum W | the L length-scale sums | sum of the coincident G | sum omega.
+constexpr int BR_LZ = BR_RR + 1, BR_BAD = BR_RR + 2;
+constexpr int BF_A = 0, BF_B = BR_T, BF_U = 2 * BR_T, BF_LD = BF_U + SGP_BATCH_MMAX,
+              BF_BAD = BF_LD + 1, BATCH_FW = BF_LD + 8;
+constexpr int BQ_W = BR_T, BATCH_REC4 = BR_T + SGP_MAXD + 8;
 struct BatchArgs {
   const double *X, *y, *mu;     // the resident rows (X column-major, ld ldx)
   int64_t ldx;
@@ -642,9 +652,15 @@ struct BatchArgs {
   double* rec3;                 // nseg records of BATCH_REC3
   const double* bnd;            // per problem d lower | d upper bounds, or nullptr (chain factor 1)
   double* gk;                   // the packed knot gradients, problem b at BP_GOFF
+  // sgp_batch_eval_fitc (sec. 0q)
+  double* fw;                   // B work slots of BATCH_FW
+  double* rec4;                 // nseg records of BATCH_REC4
 };
 // ev (or nullptr): 5 events recorded before pass 1, the m x m stage, pass 2, the finish and after
 hipError_t launch_batch_eval(const BatchArgs& a, hipStream_t s, hipEvent_t* ev);
+// the FITC evaluation's five launches (three with obj_only); ev (or nullptr): 6 events recorded
+// before K22's stage, the weighted pass 1, Bm's stage, the gradient pass, the G22 stage and after
+hipError_t launch_batch_eval_fitc(const BatchArgs& a, hipStream_t s, hipEvent_t* ev);
 // res: per problem 64 * 64 + 64 doubles, u_var (row stride 64) | u_mean - muu
 hipError_t launch_batch_post(const BatchArgs& a, double* res, hipStream_t s);
 // after launch_batch_eval with a.hk set; ev (or nullptr): 3 events recorded before the knot pass,
