@@ -42,6 +42,41 @@ int sgp_diag_store_bw(int device, int64_t bytes, int reps, int pattern, double* 
 int sgp_diag_syrk_plan(int64_t n, int64_t m, int* plan, int* workgroups, double* t_balanced,
                        double* t_packed);
 
+/* The device exp functions every covariance entry goes through, applied entry by entry by one tiny
+ * kernel that calls the very inline functions of the builders: out[i] for x[0..n).  which = 0:
+ * sgp_exp_nonpos(x), the direct-difference builder's, the batched kernels' and the scans' (x <= 0;
+ * NaN in, NaN out).  which = 1: sgp_exp_tab(fmin(fmax(x, -746), hi)), the matrix-core builder's,
+ * with the table staged in LDS and the argument clamped as that builder does; hi is the clamp's
+ * upper end (the builder passes log sigma^2; at most log(DBL_MAX) = 709.78...; ignored with which
+ * = 0).  SGP_EINVAL (before any device call) for a NULL pointer, n < 1, another `which`, or a hi
+ * that is NaN or above log(DBL_MAX). */
+int sgp_diag_exp(int device, int which, const double* x, int64_t n, double hi, double* out);
+
+/* K12 = sigma^2 exp(-1/2 |x~ - u~|^2) as the fused evaluations build it, entry by entry: X (n x d,
+ * column-major, ld ldx) and U (m x d, ld ldu) are uploaded zero-padded to n_pad = round_up(n, 128)
+ * rows and m_p = round_up(m, 128) knots, the builder's centre and span guard are set from the
+ * knots and the data's column ranges as a context sets them, and K receives the whole padded
+ * n_pad x m_p row-major matrix (rows >= n and columns >= m are +0.0).  theta as sgp_eval_vi's
+ * (sigma, the length scales, tau; tau is not used).  With r (n values; NULL: none) the builder's
+ * fused t = K^T r rides along: t receives its m_p reduced values (summed as the VI evaluation sums
+ * the builder's partial rows) and *t_rows the number of partial rows.
+ * Three knobs, 0 = the product's behaviour:
+ *   route     0: the span guard decides; 1: the matrix-core builder; 2: the direct-difference one.
+ *             *route_taken = 1 or 2.
+ *   max_rows  a cap on the workgroup rows of the builder's grid (1: one workgroup row walks every
+ *             64-row block, i.e. the persistent loop at any n).
+ *   shared_rb the leading row blocks built by the shared-occupancy launch (-1: as many as beside a
+ *             K22 chain; 0: none).
+ * K must not depend on max_rows or shared_rb; t may (its partial sums are per workgroup row) but is
+ * the same bits on a repeat.  SGP_EINVAL, before any device call: a NULL X, U, K, theta or
+ * route_taken; r without t and t_rows; n < 1, ldx < n, m < 1, ldu < m; d outside 1..32; route
+ * outside 0..2, max_rows < 0, shared_rb < -1; SGP_KERNEL_EXP or an unknown kernel; sigma or a
+ * length scale that is not positive. */
+int sgp_diag_build_knm(int device, int kernel, int d, const double* theta, const double* X,
+                       int64_t n, int64_t ldx, const double* U, int64_t m, int64_t ldu,
+                       const double* r, int route, int64_t max_rows, int64_t shared_rb, double* K,
+                       double* t, int* route_taken, int64_t* t_rows);
+
 /* Host only (no device is touched): the argument checks sgp_ego_scan (sgp.h) runs before its
  * first device call, for rows of dimension d -- the very function it calls, so a machine without
  * a GPU can test every SGP_EINVAL case.  SGP_OK or SGP_EINVAL with sgp_last_error(). */

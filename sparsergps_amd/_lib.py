@@ -83,6 +83,11 @@ PROTOTYPES = {
     "sgp_diag_store_bw": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, c_double_p]),
     "sgp_diag_syrk_plan": (C.c_int, [C.c_int64, C.c_int64, c_int_p, c_int_p, c_double_p,
                                      c_double_p]),
+    "sgp_diag_exp": (C.c_int, [C.c_int, C.c_int, c_double_p, C.c_int64, C.c_double, c_double_p]),
+    "sgp_diag_build_knm": (C.c_int, [C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, C.c_int64,
+                                     C.c_int64, c_double_p, C.c_int64, C.c_int64, c_double_p,
+                                     C.c_int, C.c_int64, C.c_int64, c_double_p, c_double_p,
+                                     c_int_p, c_int64_p]),
     "sgp_diag_ego_args": (C.c_int, [C.c_int, C.c_int, c_double_p, C.c_double, c_double_p, C.c_int64,
                                     C.c_int64, c_double_p, c_double_p, C.c_int64, C.c_int64]),
     "sgp_lap_get_f": (C.c_int, [C.c_void_p, c_double_p]),

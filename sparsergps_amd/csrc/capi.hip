@@ -119,6 +119,13 @@ int make_params(int kernel, int d, const double* theta, double delta, KernParams
   if (kernel != SGP_KERNEL_ARD)
     for (int c = 1; c < d; ++c) { kp->l[c] = kp->l[0]; kp->rl[c] = kp->rl[0]; kp->rl2[c] = kp->rl2[0]; }
   kp->lsig2 = log(kp->sig2);
+  // The matrix-core builder clamps its exponent at lsig2 so that K <= sig2.  log's rounding is
+  // |lsig2| 2^-53 relative in exp(lsig2): at sigma = 1e-150 the clamp's end came out as
+  // sig2 (1 + 2.4e-14).  Step lsig2 down until exp(lsig2) <= sig2 (1 + 2^-53); for
+  // |lsig2| < 2 (sigma in 0.37 .. 2.7) the rounding is within that already and nothing moves.
+  const long double cap = (long double)kp->sig2 * (1.0L + 0x1p-53L);
+  while (std::isfinite(kp->lsig2) && expl((long double)kp->lsig2) > cap)
+    kp->lsig2 = nextafter(kp->lsig2, -INFINITY);
   set_exp_consts(kp);
   return SGP_OK;
 }
@@ -159,6 +166,7 @@ void set_center(KernParams* kp, const double* U, int64_t m, int64_t ldu, const d
                 const double* xhi, const double* extra = nullptr, int64_t T = 0,
                 int64_t ldx = 0) {
   double span2 = 0.0;
+  bool nan = false;   // the comparisons and fmax below drop a NaN: note it here
   for (int c = 0; c < kp->d; ++c) {
     double s = 0.0, lo = U[c * ldu], hi = U[c * ldu];
     for (int64_t j = 0; j < m; ++j) {
@@ -169,21 +177,25 @@ void set_center(KernParams* kp, const double* U, int64_t m, int64_t ldu, const d
     }
     kp->ctr[c] = m > 0 ? s / (double)m : 0.0;
     if (xlo && xhi) {
+      nan = nan || xlo[c] != xlo[c] || xhi[c] != xhi[c];
       lo = xlo[c] < lo ? xlo[c] : lo;
       hi = xhi[c] > hi ? xhi[c] : hi;
     }
     for (int64_t j = 0; extra && j < T; ++j) {
       const double v = extra[j + c * ldx];
+      nan = nan || v != v;
       lo = v < lo ? v : lo;
       hi = v > hi ? v : hi;
     }
     const double e = fmax(fabs(lo - kp->ctr[c]), fabs(hi - kp->ctr[c])) * kp->rl[c];
     span2 += e * e;
   }
-  kp->span2 = span2 == span2 ? span2 : INFINITY;   // NaN coordinates: the VALU form
+  // NaN coordinates: the VALU form (the matrix-core builder's clamp would turn them into 0)
+  kp->span2 = (span2 == span2 && !nan) ? span2 : INFINITY;
 }
 
-// column ranges of an n x d column-major host matrix
+// column ranges of an n x d column-major host matrix; a NaN entry makes both ends of its column
+// NaN (set_center then keeps the builder off the matrix-core route)
 void col_range(const double* X, int64_t n, int64_t ldx, int d, std::vector<double>* lo,
                std::vector<double>* hi) {
   lo->assign((size_t)d, 0.0);
@@ -192,8 +204,8 @@ void col_range(const double* X, int64_t n, int64_t ldx, int d, std::vector<doubl
     double a = n > 0 ? X[c * ldx] : 0.0, b = a;
     for (int64_t i = 1; i < n; ++i) {
       const double v = X[i + c * ldx];
-      a = v < a ? v : a;
-      b = v > b ? v : b;
+      a = (v < a || v != v) ? v : a;
+      b = (v > b || v != v) ? v : b;
     }
     (*lo)[(size_t)c] = a;
     (*hi)[(size_t)c] = b;
@@ -961,18 +973,7 @@ int sgp_ctx_create(sgp_ctx** out, int device, const double* X, int64_t n, int64_
     delete c;
     return st;
   }
-  c->xmin.assign((size_t)d, 0.0);
-  c->xmax.assign((size_t)d, 0.0);
-  for (int q = 0; q < d; ++q) {
-    double lo = X[q * ldx], hi = X[q * ldx];
-    for (int64_t i = 1; i < n; ++i) {
-      const double v = X[i + q * ldx];
-      lo = v < lo ? v : lo;
-      hi = v > hi ? v : hi;
-    }
-    c->xmin[(size_t)q] = lo;
-    c->xmax[(size_t)q] = hi;
-  }
+  col_range(X, n, ldx, d, &c->xmin, &c->xmax);
   // X: column-major with ld = n_pad, zero padded
   std::vector<double> hx((size_t)(np_ * d), 0.0);
   for (int q = 0; q < d; ++q)
@@ -5237,6 +5238,124 @@ int sgp_diag_syrk_plan(int64_t n, int64_t m, int* plan, int* workgroups, double*
   }
   syrk_plan_info(round_up(n, SGP_TILE), round_up(m, SGP_TILE), plan, workgroups, t_balanced,
                  t_packed);
+  return SGP_OK;
+}
+
+int sgp_diag_exp(int device, int which, const double* x, int64_t n, double hi, double* out) {
+  if (!x || !out || n < 1) {
+    set_err("sgp_diag_exp: NULL argument or n < 1");
+    return SGP_EINVAL;
+  }
+  if (which != 0 && which != 1) {
+    set_err("sgp_diag_exp: which=%d is neither 0 (sgp_exp_nonpos) nor 1 (sgp_exp_tab)", which);
+    return SGP_EINVAL;
+  }
+  if (which == 1 && !(hi <= 709.782712893384)) {
+    set_err("sgp_diag_exp: hi=%g is NaN or above log(DBL_MAX)", hi);
+    return SGP_EINVAL;
+  }
+  HIPCHK(hipSetDevice(device));
+  KernParams kp;
+  memset(&kp, 0, sizeof(kp));
+  set_exp_consts(&kp);
+  StreamGuard sg;
+  HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+  DevBuf dx, dout;
+  int st = dalloc(&dx.p, n);
+  st = st ? st : dalloc(&dout.p, n);
+  if (st) return st;
+  HIPCHK(hipMemcpyAsync(dx.p, x, sizeof(double) * n, hipMemcpyHostToDevice, sg.s));
+  HIPCHK(launch_diag_exp(kp, which, hi, dx.p, n, dout.p, sg.s));
+  HIPCHK(hipMemcpyAsync(out, dout.p, sizeof(double) * n, hipMemcpyDeviceToHost, sg.s));
+  HIPCHK(hipStreamSynchronize(sg.s));
+  return SGP_OK;
+}
+
+int sgp_diag_build_knm(int device, int kernel, int d, const double* theta, const double* X,
+                       int64_t n, int64_t ldx, const double* U, int64_t m, int64_t ldu,
+                       const double* r, int route, int64_t max_rows, int64_t shared_rb, double* K,
+                       double* t, int* route_taken, int64_t* t_rows) {
+  const char* who = "sgp_diag_build_knm";
+  if (!X || !U || !K || !route_taken) {
+    set_err("%s: X, U, K or route_taken is NULL", who);
+    return SGP_EINVAL;
+  }
+  if (r && (!t || !t_rows)) {
+    set_err("%s: r is given but t or t_rows is NULL", who);
+    return SGP_EINVAL;
+  }
+  if (n < 1 || ldx < n || m < 1 || ldu < m) {
+    set_err("%s: n=%lld, ldx=%lld, m=%lld, ldu=%lld (need n >= 1, ldx >= n, m >= 1, ldu >= m)",
+            who, (long long)n, (long long)ldx, (long long)m, (long long)ldu);
+    return SGP_EINVAL;
+  }
+  if (route < 0 || route > 2 || max_rows < 0 || shared_rb < -1) {
+    set_err("%s: route=%d outside 0..2, max_rows=%lld < 0 or shared_rb=%lld < -1", who, route,
+            (long long)max_rows, (long long)shared_rb);
+    return SGP_EINVAL;
+  }
+  if (kernel == SGP_KERNEL_EXP) {
+    set_err("%s: the K12 builders support 'sqexp' and 'ard', not 'exp'", who);
+    return SGP_EINVAL;
+  }
+  KernParams kp;
+  int st = make_params(kernel, d, theta, 0.0, &kp);   // kernel, d in [1, SGP_MAXD], theta, l > 0
+  if (st) return st;
+  if (!(kp.sigma > 0.0)) {
+    set_err("%s: sigma must be positive", who);
+    return SGP_EINVAL;
+  }
+  if (route == 1 && d > 32) {
+    set_err("%s: the matrix-core builder needs d <= 32 (d=%d)", who, d);
+    return SGP_EINVAL;
+  }
+  // as sgp_ctx: the centre and the span guard from the knots and the data box
+  std::vector<double> xlo, xhi;
+  col_range(X, n, ldx, d, &xlo, &xhi);
+  set_center(&kp, U, m, ldu, xlo.data(), xhi.data());
+  if (route == 1) kp.span2 = 0.0;             // the guard (knm_mfma_ok) reads nothing else
+  else if (route == 2) kp.span2 = INFINITY;
+  *route_taken = knm_mfma_ok(kp) ? 1 : 2;
+  const int64_t np_ = round_up(n, SGP_TILE), mp = round_up(m, SGP_TILE);
+  HIPCHK(hipSetDevice(device));
+  StreamGuard sg;
+  HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+  DevBuf dX, dU, dK, dr, dts, dpart, dt;
+  st = dalloc(&dX.p, np_ * d);
+  st = st ? st : dalloc(&dU.p, mp * d);
+  st = st ? st : dalloc(&dK.p, np_ * mp);
+  if (r) {
+    st = st ? st : dalloc(&dr.p, np_);
+    st = st ? st : dalloc(&dts.p, (np_ / 64) * mp);
+    st = st ? st : dalloc(&dpart.p, 64 * mp);
+    st = st ? st : dalloc(&dt.p, mp);
+  }
+  if (st) return st;
+  std::vector<double> hx((size_t)(np_ * d), 0.0), hu((size_t)(mp * d), 0.0);
+  for (int q = 0; q < d; ++q) {
+    for (int64_t i = 0; i < n; ++i) hx[(size_t)(i + q * np_)] = X[i + q * ldx];
+    for (int64_t j = 0; j < m; ++j) hu[(size_t)(j + q * mp)] = U[j + q * ldu];
+  }
+  HIPCHK(hipMemcpyAsync(dX.p, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, sg.s));
+  HIPCHK(hipMemcpyAsync(dU.p, hu.data(), sizeof(double) * hu.size(), hipMemcpyHostToDevice, sg.s));
+  // every entry is the builder's own: start from a pattern that is neither 0 nor a covariance
+  HIPCHK(hipMemsetAsync(dK.p, 0xff, sizeof(double) * np_ * mp, sg.s));
+  std::vector<double> hr;
+  if (r) {
+    hr.assign((size_t)np_, 0.0);
+    for (int64_t i = 0; i < n; ++i) hr[(size_t)i] = r[i];
+    HIPCHK(hipMemcpyAsync(dr.p, hr.data(), sizeof(double) * np_, hipMemcpyHostToDevice, sg.s));
+  }
+  int64_t trows = 0;
+  HIPCHK(launch_build_knm_diag(kp, dX.p, np_, n, np_, dU.p, mp, m, mp, dK.p, r ? dr.p : nullptr,
+                               dts.p, &trows, shared_rb, max_rows, sg.s));
+  if (r) {
+    HIPCHK(launch_knot_reduce(dts.p, trows, mp, 1, dpart.p, 64 * mp, dt.p, false, sg.s));
+    HIPCHK(hipMemcpyAsync(t, dt.p, sizeof(double) * mp, hipMemcpyDeviceToHost, sg.s));
+  }
+  HIPCHK(hipMemcpyAsync(K, dK.p, sizeof(double) * np_ * mp, hipMemcpyDeviceToHost, sg.s));
+  HIPCHK(hipStreamSynchronize(sg.s));
+  if (t_rows) *t_rows = trows;
   return SGP_OK;
 }
 

@@ -582,7 +582,8 @@ hipError_t launch_fill_dcov(const KernParams& kp, const double* x, int64_t n, in
 static hipError_t build_knm_range(const KernParams& kp, const double* X, int64_t ldx, int64_t n,
                                   const double* U, int64_t ldu, int64_t m, int64_t mp, double* K,
                                   const double* r, double* tslab, int64_t slot0, int64_t* slots,
-                                  int64_t rb0, int64_t rb1, int wpc, hipStream_t s) {
+                                  int64_t rb0, int64_t rb1, int wpc, hipStream_t s,
+                                  int64_t max_rows = 0) {   // > 0: a cap on gy (sgp_diag_build_knm)
   static int cus = 0, occ[2][3];   // [with t][NC = 2, 4, 8]
   if (cus == 0) {
     int dev = 0;
@@ -612,6 +613,7 @@ static hipError_t build_knm_range(const KernParams& kp, const double* X, int64_t
     const int per_cu = wpc < oc ? wpc : oc;
     int64_t gy = ((int64_t)cus * per_cu) / (ncb > 0 ? ncb : 1);
     gy = gy < 1 ? 1 : (gy > rb1 - rb0 ? rb1 - rb0 : gy);
+    if (max_rows > 0 && gy > max_rows) gy = max_rows;
     dim3 grid((unsigned)ncb, (unsigned)gy);
 #define SGP_BUILD_MFMA(T, NCV)                                                                 \
   hipLaunchKernelGGL((k_build_knm_mfma<T, NCV>), grid, dim3(256), 0, s, kp, X, ldx, n, U, ldu, m, \
@@ -631,6 +633,7 @@ static hipError_t build_knm_range(const KernParams& kp, const double* X, int64_t
   }
   int64_t gy = ((int64_t)cus * wpc) / (ncb > 0 ? ncb : 1);
   gy = gy < 1 ? 1 : (gy > rb1 - rb0 ? rb1 - rb0 : gy);
+  if (max_rows > 0 && gy > max_rows) gy = max_rows;
   dim3 grid((unsigned)ncb, (unsigned)gy);
   // the VALU builder writes one t partial per row block, at tslab row rb
   if (r && slot0 != rb0) return hipErrorInvalidValue;
@@ -652,18 +655,19 @@ constexpr int BUILD_WPC_SHARED = 2;
 static hipError_t build_knm_impl(const KernParams& kp, const double* X, int64_t ldx, int64_t n,
                                  int64_t n_pad, const double* U, int64_t ldu, int64_t m,
                                  int64_t mp, double* K, const double* r, double* tslab,
-                                 int64_t shared_rb, int64_t* t_rows, hipStream_t s) {
+                                 int64_t shared_rb, int64_t* t_rows, hipStream_t s,
+                                 int64_t max_rows = 0) {
   const int64_t nrb = n_pad / 64;
   if (shared_rb > nrb) shared_rb = nrb;
   if (shared_rb < 0) shared_rb = 0;
   int64_t s1 = 0, s2 = 0;
   hipError_t e = build_knm_range(kp, X, ldx, n, U, ldu, m, mp, K, r, tslab, 0, &s1, 0, shared_rb,
-                                 BUILD_WPC_SHARED, s);
+                                 BUILD_WPC_SHARED, s, max_rows);
   if (e != hipSuccess) return e;
   // the VALU builder's partial rows are indexed by row block
   const int64_t slot0 = knm_mfma_ok(kp) ? s1 : shared_rb;
   e = build_knm_range(kp, X, ldx, n, U, ldu, m, mp, K, r, tslab, slot0, &s2, shared_rb, nrb,
-                      BUILD_WPC_FULL, s);
+                      BUILD_WPC_FULL, s, max_rows);
   if (t_rows) *t_rows = slot0 + s2;
   return e;
 }
@@ -689,6 +693,39 @@ hipError_t launch_build_knm_t(const KernParams& kp, const double* X, int64_t ldx
                               hipStream_t s, bool beside_chain) {
   return build_knm_impl(kp, X, ldx, n, n_pad, U, ldu, m, mp, K, r, tslab,
                         beside_chain ? chain_shared_rb(mp) : 0, t_rows, s);
+}
+
+hipError_t launch_build_knm_diag(const KernParams& kp, const double* X, int64_t ldx, int64_t n,
+                                 int64_t n_pad, const double* U, int64_t ldu, int64_t m,
+                                 int64_t mp, double* K, const double* r, double* tslab,
+                                 int64_t* t_rows, int64_t shared_rb, int64_t max_rows,
+                                 hipStream_t s) {
+  return build_knm_impl(kp, X, ldx, n, n_pad, U, ldu, m, mp, K, r, r ? tslab : nullptr,
+                        shared_rb < 0 ? chain_shared_rb(mp) : shared_rb, t_rows, s, max_rows);
+}
+
+namespace {
+// sgp_diag_exp: the device exp functions applied entry by entry, the table staged in LDS as
+// k_build_knm_mfma stages it and the argument clamped as its epilogue clamps it
+__global__ void __launch_bounds__(256) k_diag_exp(KernParams kp, int which, double hi,
+                                                  const double* __restrict__ x, int64_t n,
+                                                  double* __restrict__ out) {
+  __shared__ double etab[32];
+  if (threadIdx.x < 32) etab[threadIdx.x] = kp.et[threadIdx.x];
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    out[i] = which == 0 ? sgp_exp_nonpos(x[i])
+                        : sgp_exp_tab(fmin(fmax(x[i], -746.0), hi), kp, etab);
+}
+}  // namespace
+
+hipError_t launch_diag_exp(const KernParams& kp, int which, double hi, const double* x, int64_t n,
+                           double* out, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  int64_t g = (n + 255) / 256;
+  if (g > 1024) g = 1024;
+  hipLaunchKernelGGL(k_diag_exp, dim3((unsigned)g), dim3(256), 0, s, kp, which, hi, x, n, out);
+  return hipGetLastError();
 }
 
 hipError_t launch_build_kmm(const KernParams& kp, const double* U, int64_t ldu, int64_t m,

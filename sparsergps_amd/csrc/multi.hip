@@ -328,8 +328,8 @@ int multi_create(MultiCtx** out, const int* devices, int nshards, const double* 
     double lo = X[q * ldx], hi = X[q * ldx];
     for (int64_t i = 1; i < n; ++i) {
       const double v = X[i + q * ldx];
-      lo = v < lo ? v : lo;
-      hi = v > hi ? v : hi;
+      lo = (v < lo || v != v) ? v : lo;   // a NaN sticks (capi.hip col_range): the span guard
+      hi = (v > hi || v != v) ? v : hi;   // then keeps the builder off the matrix cores
     }
     mc->xmin[(size_t)q] = lo;
     mc->xmax[(size_t)q] = hi;

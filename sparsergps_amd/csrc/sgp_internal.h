@@ -65,9 +65,9 @@ struct KernParams {
   // SGP_MFMA_SPAN2_MAX the direct-difference VALU builder is used instead (knm_mfma_ok).
   double span2;
   double lsig2;          // log(sig2): folded into the builder's GEMM-form exponent
-  // sgp_exp_kp's constants as kernel arguments, so they sit in SGPRs and each Horner step is
-  // one v_fma_f64 (as literals the compiler pairs every step with a v_mov_b64): log2(e),
-  // ln2 hi/lo, then the degree-13 Taylor coefficients 1/13! .. 1/2!
+  // sgp_exp_nonpos's constants (log2(e), ln2 hi/lo, 1/13! .. 1/2!) as kernel arguments.  No
+  // device code reads them any more; they stay so that every kernel's argument block keeps its
+  // layout (set_exp_consts still fills them)
   double ec[16];
   // sgp_exp_tab's constants: 32 log2(e), ln2/32 hi/lo, 1/6! .. 1/2!, and the table 2^(j/32)
   double xt[8];
@@ -103,22 +103,6 @@ __device__ __forceinline__ double sgp_exp_tab(double x, const KernParams& kp,
   return __builtin_ldexp(__builtin_fma(t, p, t), ki >> 5);
 }
 
-// exp(x) for x already clamped to [-746, log(DBL_MAX)]: the same reduction and polynomial as
-// sgp_exp_nonpos with the constants read from kp (SGPRs).  Below -745.13 ldexp underflows to
-// 0, as exp does.
-__device__ __forceinline__ double sgp_exp_kp(double x, const KernParams& kp) {
-  const double k = __builtin_rint(x * kp.ec[0]);
-  double r = __builtin_fma(-k, kp.ec[1], x);
-  r = __builtin_fma(-k, kp.ec[2], r);
-  double p = kp.ec[3];
-#pragma unroll
-  for (int q = 4; q < 15; ++q) p = __builtin_fma(p, r, kp.ec[q]);
-  p = __builtin_fma(p, r, 1.0);
-  p = __builtin_fma(p, r, 1.0);
-  return __builtin_ldexp(p, (int)k);
-}
-
-
 // ---------------------------------------------------------------- k_cov.hip
 // Layer-1 fillers, column-major output (R layout).  x/xp are column-major on device.
 hipError_t launch_fill_cov(const KernParams& kp, const double* x, int64_t n, int64_t ldx,
@@ -139,6 +123,19 @@ hipError_t launch_build_knm_t(const KernParams& kp, const double* X, int64_t ldx
 hipError_t launch_build_knm(const KernParams& kp, const double* X, int64_t ldx, int64_t n,
                             int64_t n_pad, const double* U, int64_t ldu, int64_t m, int64_t mp,
                             double* K, hipStream_t s, bool beside_chain = false);
+// sgp_diag_build_knm: the same two launches with their knobs exposed.  shared_rb: the leading row
+// blocks built at shared occupancy (< 0: what beside_chain gives); max_rows > 0: a cap on the
+// grid's workgroup rows (1: one workgroup row walks every row block).  K does not depend on
+// either; t's partial rows do.  r == nullptr: no t.
+hipError_t launch_build_knm_diag(const KernParams& kp, const double* X, int64_t ldx, int64_t n,
+                                 int64_t n_pad, const double* U, int64_t ldu, int64_t m,
+                                 int64_t mp, double* K, const double* r, double* tslab,
+                                 int64_t* t_rows, int64_t shared_rb, int64_t max_rows,
+                                 hipStream_t s);
+// sgp_diag_exp: out[i] = sgp_exp_nonpos(x[i]) (which 0) or sgp_exp_tab(clamp(x[i], -746, hi))
+// (which 1) for i < n
+hipError_t launch_diag_exp(const KernParams& kp, int which, double hi, const double* x, int64_t n,
+                           double* out, hipStream_t s);
 // K22 = Kuu + diag_add on the diagonal, padded with identity (mp x mp, row-major).
 // diag value = ((sig2 + tau2 + delta) - diag_sub) exactly like R's make_cov(...) - tau^2 I.
 hipError_t launch_build_kmm(const KernParams& kp, const double* U, int64_t ldu, int64_t m,

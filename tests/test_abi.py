@@ -33,6 +33,7 @@ def test_header_declares_expected_api():
     assert HEADER in HEADERS and len(HEADERS) >= 2
     names = declared_functions()
     assert "sgp_diag_gj_pair" in names and "sgp_lap_set_expo" in names
+    assert "sgp_diag_exp" in names and "sgp_diag_build_knm" in names
     for must in ("sgp_make_cov", "sgp_dsig_dtheta", "sgp_ctx_create", "sgp_eval_vi",
                  "sgp_vi_phase1", "sgp_vi_phase2", "sgp_vi_finish", "sgp_last_error"):
         assert must in names
