@@ -539,6 +539,62 @@ int sgp_batch_eval_fitc(sgp_batch* b, int kernel, const double* theta, int64_t l
                         unsigned flags, const unsigned char* active, double* obj, double* grad,
                         int64_t ldg, int* status);
 
+/* Laplace fits on a batch: Poisson counts and Bernoulli classes, what
+ * optimize_gp(family = "poisson" / "bernoulli", sparse = TRUE) fits (R/optimize_gp.R:440-665).
+ *
+ * sgp_batch_lap_init: family is SGP_FAM_POISSON or SGP_FAM_BERNOULLI (SGP_FAM_GAUSSIAN and unknown
+ * values: SGP_EINVAL).  expo: nrows host values, resident like y, each finite and > 0, or NULL for
+ * 1 on every row: the reference's `m` (R/derivative_functions_of_data_likelihoods.R:7-61); it is
+ * validated for both families and read only by Poisson.  Under Bernoulli every y in any problem's
+ * range must be 0 or 1 (SGP_EINVAL names the first that is not), and sgp_batch_set_data repeats
+ * that check once the family is set.  The call allocates all the device and pinned memory a
+ * Laplace evaluation needs (the evaluation allocates nothing), among it the latent vectors,
+ * indexed by (problem, local row): sum nrow[b] doubles packed in problem order, never by resident
+ * row, so aliased row ranges (a multi-start) need nothing further.  f starts at 0.  The call may
+ * be repeated: it then replaces family and exposure and resets f.  sgp_diag_batch_lap_args
+ * (sgp_diag.h) is the same check without a device.
+ *
+ * sgp_batch_lap_set_f / sgp_batch_lap_get_f: f is packed by problem (sum nrow[b] values).  With
+ * f == NULL, fill holds B values, one per problem: the reference starts Poisson at
+ * log(mean y) - log(expo) (R/optimize_gp.R:480) and Bernoulli at 0 (R/optimize_gp.R:583).
+ *
+ * sgp_batch_eval_laplace: the arguments up to status are sgp_batch_eval_vi's, checked by the same
+ * function (sgp_diag_batch_args) before the first device call; then tol, maxit and nr_iters (B).
+ * Per problem the semantics are exactly sgp_eval_laplace's: K22 = Kuu + (tau^2 + delta) I (quirk
+ * Q1); newtrap_sparseGP (R/newtrap_sparseGP.R:6-186) warm-started from the problem's resident f:
+ * the objective at the start, one update unconditionally, then the reference's stop rule (l.100:
+ * while iter < maxit and (|obj step| > tol or any |grad psi| > tol)); obj[b] is the last NR
+ * objective, nr_iters[b] = length(objective_function_values); maxit = 0 means objective and
+ * gradient at f as given; then dlogq_dcov_par (R/laplace_approx_gradient.R:25-336) at the mode, in
+ * log theta in sgp_num_params order with the knots fixed, with the tau terms of DESIGN.md sec. 3.3
+ * and quirk Q5.  SGP_FLAG_OBJ_ONLY is NR alone (grad may be NULL); SGP_FLAG_R_DET is not read.
+ * The three m-vector solves of an evaluation take one step of iterative refinement under
+ * Bernoulli and none under Poisson, as the context route's do.  The resident
+ * f of an evaluated problem is left at the mode.
+ * status[b] = +k when the first non-positive leading minor, of order k, is in Sigma22 (K22) and
+ * -k when it is in K22 + S_Z or K22 + S_B; obj and grad of that problem are then NaN, the call
+ * returns SGP_OK, the neighbours are unaffected, and the problem's resident f is unspecified until
+ * sgp_batch_lap_set_f or sgp_batch_lap_init sets it again.
+ * Every stop decision is taken on the device from the problem's own fixed-order sums; the host
+ * reads back only the count of problems still running, once per iteration.
+ * The posterior state of a successful problem is what sgp_posterior_u gives after
+ * sgp_eval_laplace (R/newtrap_sparseGP.R:137-176): u_mean - muu = K22 (K22 + S_Z)^-1 t_Z(f) and
+ * u_var = K22 (K22 + S_B(W_prev))^-1 K22 with the loop's last, one-step-stale W, where VI and FITC
+ * leave theirs; sgp_batch_posterior_u then gives laplace_posterior_u and sgp_batch_predict gives
+ * predict_laplace(family != "gaussian") (R/laplace_approx_prediction.R:3-123): Sigma22 with
+ * tau^2 + delta on its diagonal and the constant sigma^2 + tau^2; pred_mean and pred_var are of the
+ * latent f, and the nlp output, which is my_nlp(family = "gaussian"), is not this family's score.
+ * No atomics, every sum in an order that depends on the problem alone, nothing read from another
+ * problem: obj, grad, f, nr_iters and the posterior are bit-identical whatever the batch, the
+ * position, `active`, the repeat (from the same f) and the VI / FITC calls in between. */
+int sgp_batch_lap_init(sgp_batch* b, int family, const double* expo /* NULL: 1 */);
+int sgp_batch_lap_set_f(sgp_batch* b, const double* f /* NULL: fill */, const double* fill);
+int sgp_batch_lap_get_f(sgp_batch* b, double* f);
+int sgp_batch_eval_laplace(sgp_batch* b, int kernel, const double* theta, int64_t ldt,
+                           const double* U, const int64_t* uoff, const int64_t* m, double delta,
+                           unsigned flags, const unsigned char* active, double* obj, double* grad,
+                           int64_t ldg, int* status, double tol, int maxit, int* nr_iters);
+
 /* Held-out prediction and scoring for a batch: predict_vi
  * (R/vi_functions.R:1222-1336) and my_nlp(family = "gaussian") (R/evaluation_functions.R:14-20,
  * with quirk Q23: pred_var + tau^2 as written) for every problem of the batch in three launches,

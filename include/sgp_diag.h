@@ -205,6 +205,30 @@ int sgp_diag_batch_knot_timing(struct sgp_batch* b, int enable, double* stage_ms
  * SGP_FLAG_OBJ_ONLY); enable != 0 records them from the next such call on. */
 int sgp_diag_batch_fitc_timing(struct sgp_batch* b, int enable, double* stage_ms);
 
+/* Host only: the argument checks of the batched Laplace path (sgp.h), the very
+ * functions sgp_batch_lap_init (on the batch's own y, rows and problems) and
+ * sgp_batch_eval_laplace (after sgp_diag_batch_args' stage 1; family < 0: none set) run before
+ * their first device call.  SGP_OK or SGP_EINVAL with sgp_last_error(). */
+int sgp_diag_batch_lap_args(const double* y, int64_t nrows, const int64_t* row0,
+                            const int64_t* nrow, int64_t B, int family, const double* expo);
+int sgp_diag_batch_lap_eval_args(int family, double tol, int maxit, const int* nr_iters);
+
+/* The Newton iteration's objective values of problem `prob` in the last sgp_batch_eval_laplace
+ * that evaluated it (newtrap_sparseGP's objective_function_values, as sgp_lap_objective_values
+ * gives them for a context): *count = nr_iters, of which the first
+ * min(*count, max_n, SGP_BATCH_LAP_NOBJ) are written to out (a bounded per-problem record). */
+#define SGP_BATCH_LAP_NOBJ 256
+int sgp_diag_batch_lap_objective_values(struct sgp_batch* b, int64_t prob, double* out, int max_n,
+                                        int* count);
+
+/* stage_ms (11 doubles, or NULL): the times by HIP events of the batch's last
+ * sgp_batch_eval_laplace (zeros when they were not recorded): K22's stage, the Z pass, the
+ * K22 + S_Z stage | summed over the Newton iterations: the objective pass (the first one
+ * included), the C stage, NR's part a, x2 | the gradient's part a, its vector stage, its part b
+ * and the G22 stage (zero under SGP_FLAG_OBJ_ONLY); enable != 0 records them from the next such
+ * call on. */
+int sgp_diag_batch_laplace_timing(struct sgp_batch* b, int enable, double* stage_ms);
+
 /* Host only: the argument checks of sgp_batch_set_test (stage 0: d, B and the arguments Xt ..
  * tnrow) and of sgp_batch_predict (stage 1: B and the arguments from have_test on) -- the very
  * function both run before their first device call.  have_test / have_yt: whether set_test was

@@ -10,8 +10,8 @@ from .covariance import (cov_fun_expC, cov_fun_sqrd_exp_ardC, cov_fun_sqrd_expC,
 from .evaluation import (joint_kl, joint_nlp, mc_nlp, my_kl, my_nlp, my_rmse, predict_prob,
                          score_gp)
 from .sampling import sample_gp, sample_mvn
-from .batch import (SparseGPBatch, cross_validate_gp, norm_grad_ascent_batch,
-                    norm_grad_ascent_vi_batch, optimize_gp_batch)
+from .batch import (SparseGPBatch, cross_validate_gp, laplace_grad_ascent_batch,
+                    norm_grad_ascent_batch, norm_grad_ascent_vi_batch, optimize_gp_batch)
 from .drivers import laplace_grad_ascent, norm_grad_ascent, norm_grad_ascent_vi
 from .full import (dlogp_dcov_par_full, dlogq_dcov_par_full, full_eval, full_laplace_eval,
                    laplace_grad_ascent_full, newtrapGP, norm_grad_ascent_full, obj_fun_bern_full,
@@ -47,7 +47,8 @@ __all__ = [
     "knot_prop_var", "knot_prop_error",
     "oat_knot_selection_norm_vi", "oat_knot_selection_norm", "oat_knot_selection",
     "optimize_gp",
-    "SparseGPBatch", "norm_grad_ascent_batch", "norm_grad_ascent_vi_batch", "optimize_gp_batch",
+    "SparseGPBatch", "laplace_grad_ascent_batch", "norm_grad_ascent_batch",
+    "norm_grad_ascent_vi_batch", "optimize_gp_batch",
     "cross_validate_gp",
     "my_rmse", "my_nlp", "my_kl", "predict_prob", "score_gp",
     "joint_nlp", "joint_kl", "mc_nlp", "sample_mvn", "sample_gp",

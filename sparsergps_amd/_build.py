@@ -24,9 +24,9 @@ LIB = os.path.join(LIBDIR, "libsgp.so")
 VARIANT_ROOT = os.path.join(ROOT, "tools", "ab")
 SOURCES = ["capi.hip", "k_cov.hip", "k_mfma.hip", "k_dense.hip", "k_lap.hip", "k_ego.hip",
            "k_scan.hip", "k_score.hip", "k_joint.hip", "k_pred.hip", "k_batch.hip",
-           "k_batch_fitc.hip", "multi.hip"]
+           "k_batch_fitc.hip", "k_batch_laplace.hip", "multi.hip"]
 CSRC_HEADERS = ["sgp_internal.h", "sgp_probe.h", "sgp_multi.h", "sgp_pool.h", "sgp_syrk_plan.h",
-                "sgp_quad.h", "sgp_argmax.h", "sgp_rng.h", "sgp_batch_dev.h"]
+                "sgp_quad.h", "sgp_argmax.h", "sgp_rng.h", "sgp_batch_dev.h", "sgp_lap_lik.h"]
 HEADERS = [*CSRC_HEADERS,
            os.path.join("..", "..", "include", "sgp.h"),
            os.path.join("..", "..", "include", "sgp_diag.h")]

@@ -19,6 +19,7 @@ c_int_p = C.POINTER(C.c_int)
 c_int64_p = C.POINTER(C.c_int64)
 c_ubyte_p = C.POINTER(C.c_ubyte)
 SGP_BATCH_MMAX = 64   # sgp_batch_eval_vi's largest knot count
+SGP_BATCH_LAP_NOBJ = 256   # sgp_diag_batch_lap_objective_values' record per problem
 
 SGP_OK, SGP_EINVAL, SGP_ENOTPD, SGP_EHIP, SGP_ENOMEM = 0, 1, 2, 3, 4
 KERNELS = {"sqexp": 0, "ard": 1, "exp": 2}
@@ -179,6 +180,20 @@ PROTOTYPES = {
                                       c_int64_p, c_int64_p, C.c_double, C.c_uint, c_ubyte_p,
                                       c_double_p, c_double_p, C.c_int64, c_int_p]),
     "sgp_diag_batch_fitc_timing": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    # the batch's Laplace fits: sgp_batch_eval_vi's arguments, then tol, maxit and nr_iters
+    "sgp_batch_lap_init": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    "sgp_batch_lap_set_f": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
+    "sgp_batch_lap_get_f": (C.c_int, [C.c_void_p, c_double_p]),
+    "sgp_batch_eval_laplace": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_int64, c_double_p,
+                                         c_int64_p, c_int64_p, C.c_double, C.c_uint, c_ubyte_p,
+                                         c_double_p, c_double_p, C.c_int64, c_int_p, C.c_double,
+                                         C.c_int, c_int_p]),
+    "sgp_diag_batch_lap_args": (C.c_int, [c_double_p, C.c_int64, c_int64_p, c_int64_p, C.c_int64,
+                                          C.c_int, c_double_p]),
+    "sgp_diag_batch_lap_eval_args": (C.c_int, [C.c_int, C.c_double, C.c_int, c_int_p]),
+    "sgp_diag_batch_lap_objective_values": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, C.c_int,
+                                                      c_int_p]),
+    "sgp_diag_batch_laplace_timing": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
     # held-out prediction and scoring for a batch (Xt, ntest, ldxt, yt, mut, trow0, tnrow)
     "sgp_batch_set_test": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, c_double_p,
                                      c_double_p, c_int64_p, c_int64_p]),

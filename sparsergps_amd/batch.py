@@ -21,6 +21,13 @@
                                vi = False of optimize_gp_batch / cross_validate_gp fits; predict and
                                score then give predict_laplace(family = "gaussian")
 
+  SparseGPBatch.lap_init / set_f / get_f / eval_laplace
+                               Poisson and Bernoulli problems (newtrap_sparseGP and dlogq_dcov_par per
+                               problem), which laplace_grad_ascent_batch ascends
+                               on and family = "poisson" / "bernoulli" of optimize_gp_batch /
+                               cross_validate_gp fit; predict and score then give
+                               predict_laplace(family != "gaussian") and that family's my_nlp
+
 Per problem the semantics are the single fit's (drivers._ascent, the knots fixed or moved with
 theta: optimize_gp's xu_opt = "fixed" / "simultaneous", R/optimize_gp.R:299-333, 378-412); a problem
 that meets its stop rule is retired through the evaluation's `active` mask while the others go
@@ -68,6 +75,7 @@ class SparseGPBatch:
         self._lib = _lib.lib()
         self._h = C.c_void_p()
         self._state = [None] * self.B      # knot count of the last successful evaluation
+        self._kind = [None] * self.B       # and whether it was a Gaussian or a Laplace one
         i64 = lambda a: a.ctypes.data_as(_lib.c_int64_p)   # noqa: E731
         _lib.check(self._lib.sgp_batch_create(
             C.byref(self._h), 0 if device is None else int(device), _lib.dptr(X), n, n, d,
@@ -116,6 +124,7 @@ class SparseGPBatch:
         _lib.check(self._lib.sgp_batch_set_data(self._h, _lib.dptr(y), _lib.dptr(mu)))
         self.y, self.mu = y, mu
         self._state = [None] * self.B
+        self._kind = [None] * self.B
 
     # ------------------------------------------------------------------ evaluation
     def eval_raw(self, cov_fun, theta, xus, delta, flags, active, obj, grad, status):
@@ -126,9 +135,10 @@ class SparseGPBatch:
         self._eval(cov_fun, theta, xus, delta, flags, active, obj, grad, status)
 
     def _eval(self, cov_fun, theta, xus, delta, flags, active, obj, grad, status, knots=False,
-              bounds=None, fitc=False):
+              bounds=None, fitc=False, laplace=None):
         """sgp_batch_eval_vi, with knots sgp_batch_eval_vi_knots (bounds: B x 2d or None), with
-        fitc sgp_batch_eval_fitc; returns (grad_knot packed like U, uoff, m) with knots."""
+        fitc sgp_batch_eval_fitc, with laplace = (tol, maxit, nr_iters) sgp_batch_eval_laplace;
+        returns (grad_knot packed like U, uoff, m) with knots."""
         self._need()
         theta = np.ascontiguousarray(theta, dtype=np.float64)
         on = [active is None or bool(active[b]) for b in range(self.B)]
@@ -153,6 +163,9 @@ class SparseGPBatch:
             bd = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.float64)
             st = self._lib.sgp_batch_eval_vi_knots(*args, None if bd is None else _lib.dptr(bd),
                                                    _lib.dptr(gk))
+        elif laplace is not None:
+            st = self._lib.sgp_batch_eval_laplace(*args, laplace[0], laplace[1],
+                                                  laplace[2].ctypes.data_as(_lib.c_int_p))
         elif fitc:
             st = self._lib.sgp_batch_eval_fitc(*args)
         else:
@@ -161,6 +174,7 @@ class SparseGPBatch:
         for b in range(self.B):
             if on[b] and status[b] == 0 and not (fitc and np.isnan(obj[b])):
                 self._state[b] = int(m[b])
+                self._kind[b] = "laplace" if laplace is not None else "gaussian"
         return gk, uoff, m
 
     def eval_vi(self, cov_pars, cov_fun, xus, delta=1e-6, active=None, obj_only=False,
@@ -210,6 +224,97 @@ class SparseGPBatch:
         out = np.zeros(5)
         _lib.check(self._lib.sgp_diag_batch_fitc_timing(self._h, int(bool(enable)),
                                                         _lib.dptr(out)))
+        return out
+
+    # ------------------------------------------------------------------ Laplace (sec. 0s)
+    def lap_init(self, family, expo=None):
+        """sgp_batch_lap_init: family "poisson" or "bernoulli"; expo: n positive values (the
+        reference's m, read by Poisson only), a scalar, or None for 1 on every row.  Allocates
+        what eval_laplace needs and sets every problem's latent f to 0; may be repeated."""
+        self._need()
+        if family not in _lib.FAMILIES:
+            raise ValueError(f"family must be one of {sorted(_lib.FAMILIES)}, not {family!r}")
+        ex = None if expo is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(expo, dtype=np.float64), (self.n,)))
+        _lib.check(self._lib.sgp_batch_lap_init(self._h, _lib.FAMILIES[family],
+                                                None if ex is None else _lib.dptr(ex)))
+        self.family, self.expo = family, ex
+        self._foff = np.concatenate([[0], np.cumsum(self.nrow)]).astype(np.int64)
+
+    def _need_lap(self):
+        self._need()
+        if getattr(self, "family", None) is None:
+            raise RuntimeError("SparseGPBatch: call lap_init first")
+
+    def set_f(self, f=None, fill=None):
+        """The problems' latent vectors (sgp_batch_lap_set_f): f a list of B arrays (n_b values
+        each) or one packed array of sum n_b values; or fill, one value per problem (the
+        reference starts Poisson at log(mean y) - log(expo) and Bernoulli at 0)."""
+        self._need_lap()
+        if (f is None) == (fill is None):
+            raise ValueError("set_f: give f or fill")
+        if f is not None:
+            if isinstance(f, (list, tuple)):
+                f = np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1) for v in f])
+            v = np.ascontiguousarray(np.asarray(f, dtype=np.float64).reshape(-1))
+            if v.size != self._foff[-1]:
+                raise ValueError(f"set_f: {v.size} values for {self._foff[-1]} rows")
+            _lib.check(self._lib.sgp_batch_lap_set_f(self._h, _lib.dptr(v), None))
+        else:
+            v = np.ascontiguousarray(np.broadcast_to(np.asarray(fill, dtype=np.float64),
+                                                     (self.B,)))
+            _lib.check(self._lib.sgp_batch_lap_set_f(self._h, None, _lib.dptr(v)))
+
+    def get_f(self):
+        """The problems' latent vectors, a list of B arrays (after eval_laplace: the modes)."""
+        self._need_lap()
+        v = np.zeros(int(self._foff[-1]) + 1)
+        _lib.check(self._lib.sgp_batch_lap_get_f(self._h, _lib.dptr(v)))
+        return [v[self._foff[b]:self._foff[b + 1]].copy() for b in range(self.B)]
+
+    def eval_laplace_raw(self, cov_fun, theta, xus, delta, flags, active, obj, grad, status, tol,
+                         maxit, nr_iters):
+        """sgp_batch_eval_laplace on caller-owned arrays, as eval_raw, with nr_iters (B, int32)."""
+        self._need_lap()
+        self._eval(cov_fun, theta, xus, delta, flags, active, obj, grad, status,
+                   laplace=(float(tol), int(maxit), nr_iters))
+
+    def eval_laplace(self, cov_pars, cov_fun, xus, delta=1e-6, active=None, obj_only=False,
+                     tol=1e-6, maxit=1000):
+        """One Laplace evaluation of the batch (sgp_batch_eval_laplace): per problem
+        newtrap_sparseGP warm-started from its resident f, then dlogq_dcov_par at the mode, as
+        SparseGPContext.eval_laplace gives them for one.  Returns what eval_vi returns plus
+        nr_iters: (obj[B], grad, status[B], nr_iters[B]); obj is the last NR objective; status < 0
+        names Sigma22 + t(Sigma12) %*% ZSig12 or the B-weighted one.  The resident f is left at the
+        mode (unspecified for a problem with status != 0 until set_f).  posterior_u, predict and
+        score afterwards are laplace_posterior_u and predict_laplace(family != "gaussian")."""
+        nr = np.zeros(self.B, dtype=np.int32)
+
+        def run(cov_fun, theta, xus, delta, flags, active, obj, g, status):
+            self.eval_laplace_raw(cov_fun, theta, xus, delta, flags, active, obj, g, status, tol,
+                                  maxit, nr)
+        obj, grads, status = self._eval_pars(run, cov_pars, cov_fun, xus, delta, active, obj_only,
+                                             False)
+        return obj, grads, status, nr
+
+    def lap_objective_values(self, b):
+        """newtrap_sparseGP's objective_function_values of problem b in the last eval_laplace
+        that evaluated it (the first 256 of them)."""
+        self._need_lap()
+        out, cnt = np.zeros(_lib.SGP_BATCH_LAP_NOBJ), C.c_int(0)
+        _lib.check(self._lib.sgp_diag_batch_lap_objective_values(
+            self._h, int(b), _lib.dptr(out), out.size, C.byref(cnt)))
+        return out[:min(cnt.value, out.size)].copy()
+
+    def laplace_stage_ms(self, enable=True):
+        """HIP-event times (ms) of the last eval_laplace's eleven stages (K22, the Z pass, the
+        K22 + S_Z stage | summed over the Newton iterations: the objective pass, the C stage, NR's
+        part a, x2 | the gradient's part a, its vector stage, part b, the G22 stage); records
+        from the next one on."""
+        self._need()
+        out = np.zeros(11)
+        _lib.check(self._lib.sgp_diag_batch_laplace_timing(self._h, int(bool(enable)),
+                                                           _lib.dptr(out)))
         return out
 
     def _named(self, cov_pars, cov_fun, g, on):
@@ -391,15 +496,26 @@ class SparseGPBatch:
                 {"pred_mean": pm[off[b]:off[b] + nr[b]].reshape(-1, 1).copy(),
                  "pred_var": pv[off[b]:off[b] + nr[b]].copy()} for b in range(self.B)]
 
-    def score(self, active=None):
+    def score(self, active=None, par=None):
         """score_gp(vi = True) (vi = False after eval_fitc) for every active problem on its test
         rows: a list of {"pred",
         "nlp", "median_nlp", "mean_nlp", "rmse", "srmse", "n_nan"} dicts (None for inactive
-        problems), the nlp with each problem's own tau."""
+        problems), the nlp with each problem's own tau.  Where the active problems' posteriors are
+        Laplace ones (eval_laplace) the dicts are score_gp's for that family: predict, then one
+        call of the quadrature (my_nlp's, sgp_nlp) over the packed rows.  par: one entry per
+        problem as score_gp's par ({"m": ...} for Poisson; None: m = 1), read by Laplace problems
+        only."""
         self._need()
         test = getattr(self, "_test", None)
         if test is not None and test[3] is None:
             raise ValueError("SparseGPBatch.score: set_test was given no y_test")
+        on = [active is None or bool(active[b]) for b in range(self.B)]
+        kinds = {self._kind[b] for b in range(self.B) if on[b]}
+        if "laplace" in kinds:
+            if kinds != {"laplace"}:
+                raise ValueError("SparseGPBatch.score: the active problems mix Gaussian and "
+                                 "Laplace posteriors; score them in two calls")
+            return self._score_laplace(active, on, par)
         (r0, nr, off, yt), pm, pv, nlp, stats = self._run_predict(active, True)
         out = []
         for b in range(self.B):
@@ -419,6 +535,46 @@ class SparseGPBatch:
                         "median_nlp": float(np.median(fin)) if fin.size else float("nan"),
                         "mean_nlp": float(st[0] / st[1]) if st[1] > 0 else float("nan"),
                         "rmse": rmse, "srmse": rmse / sd, "n_nan": int(st[2])})
+        return out
+
+    def _score_laplace(self, active, on, par):
+        from .evaluation import _nlp, _score_par
+        (r0, nr, off, yt), pm, pv, _, _ = self._run_predict(active, False)
+        if par is not None and len(par) != self.B:
+            raise ValueError(f"SparseGPBatch.score: {len(par)} par entries for {self.B} problems")
+        idx = [b for b in range(self.B) if on[b] and nr[b] > 0]
+        ys, expo = [], []
+        for b in idx:
+            n = int(nr[b])
+            ys.append(yt[r0[b]:r0[b] + n])
+            p, ex = _score_par(self.family, None if par is None else par[b])
+            expo.append(np.full(n, p) if ex is None else ex)
+            if expo[-1].size != n:
+                raise ValueError(f"problem {b}: par['m'] has {expo[-1].size} values for {n} rows")
+        nlp_all = np.zeros(0)
+        if idx:
+            rows = np.concatenate([np.arange(off[b], off[b] + nr[b]) for b in idx])
+            nlp_all, _ = _nlp(self.family, np.concatenate(ys), pm[rows], pv[rows], 1.0,
+                              np.concatenate(expo) if self.family == "poisson" else None)
+        out, at = [], 0
+        for b in range(self.B):
+            if not on[b]:
+                out.append(None)
+                continue
+            n, o = int(nr[b]), int(off[b])
+            v = nlp_all[at:at + n].copy()
+            at += n
+            y = yt[r0[b]:r0[b] + n]
+            mean = pm[o:o + n]
+            fin = v[np.isfinite(v)]
+            rmse = float(np.sqrt(np.sum((mean - y) ** 2) / n)) if n else float("nan")
+            sd = float(np.std(y, ddof=1)) if n > 1 else float("nan")
+            out.append({"pred": {"pred_mean": mean.reshape(-1, 1).copy(),
+                                 "pred_var": pv[o:o + n].copy()},
+                        "nlp": v,
+                        "median_nlp": float(np.median(fin)) if fin.size else float("nan"),
+                        "mean_nlp": float(fin.mean()) if fin.size else float("nan"),
+                        "rmse": rmse, "srmse": rmse / sd, "n_nan": int(np.sum(np.isnan(v)))})
         return out
 
     def predict_stage_ms(self, enable=True):
@@ -531,6 +687,50 @@ def norm_grad_ascent_batch(cov_par_starts, cov_fun, xus, batch, muus=None, opt=N
             batch.close()
 
 
+_ERR_LAP_KNOTS = ('Laplace batches have no knot gradient: xu_opt must be "fixed" '
+                  '(use laplace_grad_ascent or optimize_gp to move knots)')
+
+
+def laplace_grad_ascent_batch(cov_par_starts, cov_fun, xus, batch, muus=None, opt=None,
+                              dcov_fun_dknot=None, xu_opt="fixed", knot_opt=None,
+                              family="poisson", expo=None, ff=None):
+    """B laplace_grad_ascent runs (R/laplace_gradient_ascent.R:10-623, Poisson or Bernoulli) in
+    lockstep on one batch: every iteration is one batch.eval_laplace call over the problems still
+    running, each problem's Newton iteration warm-started from its previous mode on the device.
+    The arguments are norm_grad_ascent_batch's, then family ("poisson" / "bernoulli"), expo (the
+    exposure of the batch's rows, as SparseGPBatch.lap_init takes it; for a list of problems one
+    entry per problem) and ff, the per-problem starts of the latent f (a list of B arrays or
+    scalars; None: 0); opt's tol_nr / maxit_nr (1e-6 / 1000) bound the Newton iteration.  Returns
+    a list of the dicts laplace_grad_ascent returns ("fmax", "u_mean", "u_var", "nr_iter", ...).
+    xu_opt other than "fixed" is refused: Laplace batches have no knot gradient."""
+    if family not in _lib.FAMILIES:
+        raise ValueError(f"family must be one of {sorted(_lib.FAMILIES)}, not {family!r}")
+    if not (dcov_fun_dknot is None or dcov_fun_dknot is False or
+            (isinstance(dcov_fun_dknot, float) and np.isnan(dcov_fun_dknot))):
+        raise ValueError("laplace_grad_ascent_batch: knot gradients are not supported "
+                         "(dcov_fun_dknot must be None)")
+    if xu_opt != "fixed":
+        raise ValueError("laplace_grad_ascent_batch: " + _ERR_LAP_KNOTS)
+    o = _opts(opt, {"maxit_nr": 1000, "tol_nr": 1e-6})
+    own = not hasattr(batch, "eval_laplace")
+    if own:
+        if expo is not None and isinstance(expo, (list, tuple)):
+            expo = np.concatenate([np.broadcast_to(np.asarray(e, dtype=np.float64),
+                                                   (np.asarray(p[1]).size,))
+                                   for e, p in zip(expo, batch)])
+        batch = SparseGPBatch.from_problems(batch)
+    try:
+        if own or getattr(batch, "family", None) != family or expo is not None:
+            batch.lap_init(family, expo)
+        if ff is not None:
+            batch.set_f([np.broadcast_to(np.asarray(ff[b], dtype=np.float64),
+                                         (int(batch.nrow[b]),)) for b in range(batch.B)])
+        return _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o, objective="laplace")
+    finally:
+        if own:
+            batch.close()
+
+
 def _bounded(t, bounds):
     """drivers._bounded in the reference's order of operations, a product with the reciprocal
     (trans_fun, covariance_function_derivatives.R:191-197): a last-bit difference in a knot shows
@@ -560,11 +760,16 @@ def _knot_keep(knot_opt, B, ms, d):
 
 def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o, simul=False, knot_opt=None,
               objective="vi"):
-    """objective: "vi" (batch.eval_vi / eval_vi_knots) or "fitc" (batch.eval_fitc, knots fixed)."""
-    if objective not in ("vi", "fitc"):
-        raise ValueError(f'_lockstep: objective must be "vi" or "fitc", not {objective!r}')
+    """objective: "vi" (batch.eval_vi / eval_vi_knots), "fitc" (batch.eval_fitc, knots fixed) or
+    "laplace" (batch.eval_laplace with o's tol_nr / maxit_nr, knots fixed)."""
+    if objective not in ("vi", "fitc", "laplace"):
+        raise ValueError(f'_lockstep: objective must be "vi", "fitc" or "laplace", not '
+                         f'{objective!r}')
     if simul and objective == "fitc":
         raise ValueError(_ERR_FITC_KNOTS)
+    if simul and objective == "laplace":
+        raise ValueError(_ERR_LAP_KNOTS)
+    nr_iter = [[] for _ in range(batch.B)]
     B = batch.B
     if len(cov_par_starts) != B or len(xus) != B:
         raise ValueError(f"norm_grad_ascent_vi_batch: {B} problems, {len(cov_par_starts)} "
@@ -603,6 +808,12 @@ def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o, simul=False, knot_op
         if simul:
             ob, gr, kg, st = batch.eval_vi_knots(pars, cov_fun, xus, o["delta"], active=active,
                                                  bounds=bounds)
+        elif objective == "laplace":
+            ob, gr, st, nr = batch.eval_laplace(pars, cov_fun, xus, o["delta"], active=active,
+                                                tol=o["tol_nr"], maxit=o["maxit_nr"])
+            for b in range(B):
+                if active[b] and st[b] == 0:
+                    nr_iter[b].append(int(nr[b]))
         elif objective == "fitc":
             ob, gr, st = batch.eval_fitc(pars, cov_fun, xus, o["delta"], active=active)
         else:
@@ -672,6 +883,7 @@ def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o, simul=False, knot_op
     u_means, u_vars = [None] * B, [None] * B
     if any(e is None for e in error):
         u_means, u_vars = batch.posterior_u(muus)
+    fmax = batch.get_f() if objective == "laplace" else None
     out = []
     for b in range(B):
         xy, _, mu = data[b]
@@ -683,6 +895,9 @@ def _lockstep(cov_par_starts, cov_fun, xus, batch, muus, o, simul=False, knot_op
                "cov_fun": cov_fun, "xy": np.array(xy), "mu": np.array(mu), "muu": muus[b],
                "u_mean": None if error[b] else u_means[b],
                "u_var": None if error[b] else u_vars[b]}
+        if objective == "laplace":       # laplace_grad_ascent's dict (drivers.py)
+            res["fmax"] = None if error[b] else fmax[b]
+            res["nr_iter"] = np.array(nr_iter[b])
         if error[b] is not None:
             res["error"] = error[b]
         out.append(res)
@@ -716,8 +931,28 @@ _ERR_Q10 = ('xu_opt = "simultaneous" passes cov_fun = "sqexp" to the driver '
             '(R/optimize_gp.R:320, 399), which cannot take an "ard" fit\'s cov_par; use "fixed"')
 
 
+def _family_check(family, vi, xu_opt, who):
+    """The refusals of a non-Gaussian family: optimize_gp's for vi = TRUE, and the knots fixed."""
+    from .optimize import ERR_VI
+    if family not in ("gaussian", "poisson", "bernoulli"):
+        raise ValueError(f"family must be gaussian, poisson or bernoulli, not {family!r}")
+    if family != "gaussian":
+        if vi:
+            raise ValueError(f'{who}: family = "{family}" needs vi = False ({ERR_VI})')
+        if xu_opt != "fixed":
+            raise ValueError(f"{who}: " + _ERR_LAP_KNOTS)
+
+
+def _lap_starts(family, ys, expos):
+    """optimize_gp's starts of the latent f: log(mean y) - log(expo) for Poisson
+    (R/optimize_gp.R:480), 0 for Bernoulli (l.583)."""
+    if family == "poisson":
+        return [np.full(y.size, np.log(y.mean())) - np.log(e) for y, e in zip(ys, expos)]
+    return [np.zeros(y.size) for y in ys]
+
+
 def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None, xu_opt="fixed",
-                      vi=True):
+                      vi=True, family="gaussian", expo=None):
     """optimize_gp(y, xy, cov_fun, cov_par_start, mu, family = "gaussian", sparse = TRUE,
     xu_opt, xu, muu, vi, opt) for each (xy, y, mu) of `problems`, fitted in lockstep on
     one batch.  vi: True (the default here, as before) for the Titsias ELBO; False for FITC, the
@@ -726,8 +961,16 @@ def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None, 
     xu_opt = "simultaneous" raises a ValueError (FITC batches have no knot gradient yet).  xu_opt: "fixed" or "simultaneous" (all knots move, R/optimize_gp.R:396-412; with
     cov_fun = "ard" optimize_gp's quirk-Q10 ValueError); "oat" and "random" are refused.  cov_par_start, xu and muu: one value for all problems or a list with
     one per problem.  Returns a list of optimize_gp's {"results", "sparse", "family", "delta",
-    "xu_init"} dicts (or its error strings), which predict_gp, predictor_gp and score_gp take."""
+    "xu_init"} dicts (or its error strings), which predict_gp, predictor_gp and score_gp take.
+
+    family: "gaussian" (the default, as before), or "poisson" / "bernoulli" for
+    optimize_gp(family, sparse = TRUE, xu_opt = "fixed")'s Laplace fits: these
+    need vi = False (vi = True raises a ValueError with optimize_gp's message) and
+    xu_opt = "fixed"; expo: the Poisson exposure, one entry (a scalar or n_b values) per problem
+    or one scalar for all (optimize_gp's a; None: 1); the latent f starts where optimize_gp
+    starts it."""
     from .optimize import ERR_COV, ERR_GA, ERR_MAXKNOT, OPT_MASTER
+    _family_check(family, vi, xu_opt, "optimize_gp_batch")
     simul = _xu_opt(xu_opt, "optimize_gp_batch")
     if simul and not vi:
         raise ValueError("optimize_gp_batch: " + _ERR_FITC_KNOTS)
@@ -752,18 +995,30 @@ def optimize_gp_batch(problems, cov_fun, cov_par_start, xu, muu=None, opt=None, 
         xy = _mat(prob[0], n)
         u, mb = _knots_and_muu(xus[b], muus[b])
         keep.append((b, (xy, prob[1], prob[2] if len(prob) > 2 else None), u, mb))
-    if keep:
+    if keep and family != "gaussian":
+        ys = [np.asarray(p[1], dtype=np.float64).reshape(-1) for _, p, _, _ in keep]
+        per = expo if isinstance(expo, (list, tuple)) else [expo] * B
+        if len(per) != B:
+            raise ValueError("optimize_gp_batch: expo must be one value or one per problem")
+        expos = [np.broadcast_to(np.asarray(1.0 if per[b] is None else per[b], dtype=np.float64),
+                                 (y.size,)) for (b, *_), y in zip(keep, ys)]
+        res = laplace_grad_ascent_batch(
+            [starts[b] for b, *_ in keep], cov_fun, [u for _, _, u, _ in keep],
+            [p for _, p, _, _ in keep], [mb for *_, mb in keep], o, family=family, expo=expos,
+            ff=_lap_starts(family, ys, expos))
+    elif keep:
         driver = norm_grad_ascent_vi_batch if vi else norm_grad_ascent_batch
         res = driver([starts[b] for b, *_ in keep], cov_fun, [u for _, _, u, _ in keep],
                      [p for _, p, _, _ in keep], [mb for *_, mb in keep], o, xu_opt=xu_opt)
+    if keep:
         for (b, _, u, _), r in zip(keep, res):
-            out[b] = {"results": r, "sparse": True, "family": "gaussian", "delta": o["delta"],
+            out[b] = {"results": r, "sparse": True, "family": family, "delta": o["delta"],
                       "xu_init": u}
     return out
 
 
 def cross_validate_gp(y, xy, cov_fun, cov_par_start, xu, folds=5, mu=None, muu=None, opt=None,
-                      rng=None, xu_opt="fixed", vi=True):
+                      rng=None, xu_opt="fixed", vi=True, family="gaussian", expo=None):
     """k-fold cross-validation of optimize_gp(family = "gaussian", sparse = TRUE, vi,
     xu_opt): every fold's fit runs in lockstep on one batch and every fold's held-out rows are
     scored on it (SparseGPBatch.score), without the posteriors leaving the device.  vi: True (the
@@ -783,8 +1038,14 @@ def cross_validate_gp(y, xy, cov_fun, cov_par_start, xu, folds=5, mu=None, muu=N
     Returns {"folds": [{"model": an optimize_gp-shaped dict (predict_gp / score_gp take it),
     "score": score_gp's dict for the held-out rows, or the fit's error, "test_rows": indices}],
     "mean_nlp", "median_nlp" (over all held-out rows' finite nlp), "rmse" (over all held-out
-    rows), "fold_id"}; the pooled figures cover the folds that were scored."""
+    rows), "fold_id"}; the pooled figures cover the folds that were scored.
+
+    family: "gaussian" (the default, as before), or "poisson" / "bernoulli" for the Laplace fits
+    of optimize_gp_batch(family = ...) (vi = False and xu_opt = "fixed" are needed) scored by
+    score_gp's figures for that family; expo: the Poisson exposure of the n rows (a scalar or n
+    values; None: 1), split by rows like y and passed to the score as par = {"m": ...}."""
     from .optimize import ERR_COV, ERR_GA, ERR_MAXKNOT, OPT_MASTER
+    _family_check(family, vi, xu_opt, "cross_validate_gp")
     simul = _xu_opt(xu_opt, "cross_validate_gp")
     if simul and not vi:
         raise ValueError("cross_validate_gp: " + _ERR_FITC_KNOTS)
@@ -834,18 +1095,29 @@ def cross_validate_gp(y, xy, cov_fun, cov_par_start, xu, folds=5, mu=None, muu=N
         mbs.append(mb)
     batch = SparseGPBatch.from_problems(problems)
     try:
-        driver = norm_grad_ascent_vi_batch if vi else norm_grad_ascent_batch
-        res = driver(starts, cov_fun, us, batch, mbs, o, xu_opt=xu_opt)
+        pars = None
+        if family != "gaussian":
+            ex = np.broadcast_to(np.asarray(1.0 if expo is None else expo, dtype=np.float64), (n,))
+            batch.lap_init(family, np.concatenate([ex[tr] for tr in train_rows]))
+            res = laplace_grad_ascent_batch(
+                starts, cov_fun, us, batch, mbs, o, family=family,
+                ff=_lap_starts(family, [y[tr] for tr in train_rows],
+                               [ex[tr] for tr in train_rows]))
+            if family == "poisson":
+                pars = [{"m": ex[te]} for te in test_rows]
+        else:
+            driver = norm_grad_ascent_vi_batch if vi else norm_grad_ascent_batch
+            res = driver(starts, cov_fun, us, batch, mbs, o, xu_opt=xu_opt)
         ok = np.array(["error" not in r for r in res], dtype=np.uint8)
         scores = [None] * B
         if ok.any():
             batch.set_test_problems(tests)
-            scores = batch.score(ok)
+            scores = batch.score(ok) if pars is None else batch.score(ok, par=pars)
     finally:
         batch.close()
     out, nlps, errs = [], [], []
     for b in range(B):
-        model = {"results": res[b], "sparse": True, "family": "gaussian", "delta": o["delta"],
+        model = {"results": res[b], "sparse": True, "family": family, "delta": o["delta"],
                  "xu_init": us[b]}
         out.append({"model": model, "score": scores[b] if ok[b] else res[b]["error"],
                     "test_rows": test_rows[b]})

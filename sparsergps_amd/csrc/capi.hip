@@ -5404,6 +5404,21 @@ struct sgp_batch {
   int* h_act = nullptr;              // pinned
   hipEvent_t pev[4] = {nullptr, nullptr, nullptr, nullptr};
   float pstage_ms[3] = {0.f, 0.f, 0.f};
+  // sgp_batch_lap_init / sgp_batch_eval_laplace (sec. 0s): the family (-1: none set), the
+  // exposure, the latent vectors packed by problem (loff: B + 1 offsets), the work slots, the
+  // control blocks, the vector records and the Newton iteration's objective values
+  int lap_family = -1;
+  std::vector<double> hy;              // y on the host: the Bernoulli check of lap_init / set_data
+  std::vector<int64_t> loff;
+  double *lexpo = nullptr, *lf = nullptr, *lzv = nullptr, *llw = nullptr, *llc = nullptr,
+         *llrec = nullptr, *lobjs = nullptr;
+  int64_t* lseg_loc = nullptr;
+  int* lcount = nullptr;
+  double* h_lc = nullptr;              // pinned
+  int* h_count = nullptr;              // pinned
+  hipEvent_t lev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  double lstage_ms[11] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};
+  bool ltiming = false;
 };
 
 namespace {
@@ -5626,6 +5641,65 @@ int batch_check_test(int stage, int d, int64_t B, const double* Xt, int64_t ntes
   return SGP_OK;
 }
 
+// Under the Bernoulli family every y in a problem's range is 0 or 1
+// (R/derivative_functions_of_data_likelihoods.R:86-184 take y as a class label).
+int batch_check_bern(const char* who, const double* y, const int64_t* row0, const int64_t* nrow,
+                     int64_t B) {
+  for (int64_t p = 0; p < B; ++p)
+    for (int64_t i = row0[p]; i < row0[p] + nrow[p]; ++i)
+      if (!(y[i] == 0.0 || y[i] == 1.0)) {
+        set_err("%s: y[%lld] = %g (problem %lld) is not 0 or 1 under SGP_FAM_BERNOULLI", who,
+                (long long)i, y[i], (long long)p);
+        return SGP_EINVAL;
+      }
+  return SGP_OK;
+}
+
+// The argument checks of sgp_batch_lap_init, made before its first device call;
+// sgp_diag_batch_lap_args is this function.
+int batch_check_lap(const double* y, int64_t nrows, const int64_t* row0, const int64_t* nrow,
+                    int64_t B, int family, const double* expo) {
+  if (family != SGP_FAM_POISSON && family != SGP_FAM_BERNOULLI) {
+    set_err("sgp_batch_lap_init: family=%d (need SGP_FAM_POISSON or SGP_FAM_BERNOULLI)", family);
+    return SGP_EINVAL;
+  }
+  if (!y || !row0 || !nrow || B < 1 || nrows < 1) {
+    set_err("sgp_batch_lap_init: y, row0 and nrow must not be NULL");
+    return SGP_EINVAL;
+  }
+  for (int64_t p = 0; p < B; ++p)
+    if (nrow[p] < 1 || row0[p] < 0 || row0[p] > nrows - nrow[p]) {
+      set_err("sgp_batch: problem %lld's rows [%lld, %lld) leave [0, %lld)", (long long)p,
+              (long long)row0[p], (long long)(row0[p] + nrow[p]), (long long)nrows);
+      return SGP_EINVAL;
+    }
+  if (expo)
+    for (int64_t i = 0; i < nrows; ++i)
+      if (!std::isfinite(expo[i]) || !(expo[i] > 0.0)) {
+        set_err("sgp_batch_lap_init: expo[%lld] = %g is not a positive finite number",
+                (long long)i, expo[i]);
+        return SGP_EINVAL;
+      }
+  if (family == SGP_FAM_BERNOULLI) return batch_check_bern("sgp_batch_lap_init", y, row0, nrow, B);
+  return SGP_OK;
+}
+
+// What sgp_batch_eval_laplace checks beyond batch_check_eval
+int batch_check_lap_eval(int family, double tol, int maxit, const int* nr_iters) {
+  if (family < 0) {
+    set_err("sgp_batch_eval_laplace: no family set (call sgp_batch_lap_init first)");
+    return SGP_EINVAL;
+  }
+  if (!(tol >= 0.0) || !std::isfinite(tol) || maxit < 0) {
+    set_err("invalid Laplace controls (tol=%g, maxit=%d)", tol, maxit);
+    return SGP_EINVAL;
+  }
+  if (!nr_iters) { set_err("sgp_batch_eval_laplace: nr_iters must not be NULL"); return SGP_EINVAL; }
+  return SGP_OK;
+}
+
+void batch_free_lap(sgp_batch* b);
+
 void batch_free_test(sgp_batch* b) {
   for (double** p : {&b->Xt, &b->yt, &b->mut, &b->pw, &b->prec, &b->pout})
     if (*p) { (void)hipFree(*p); *p = nullptr; }
@@ -5638,6 +5712,18 @@ void batch_free_test(sgp_batch* b) {
   b->have_test = b->have_yt = false;
 }
 
+void batch_free_lap(sgp_batch* b) {
+  for (double** p : {&b->lexpo, &b->lf, &b->lzv, &b->llw, &b->llc, &b->llrec, &b->lobjs})
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+  if (b->lseg_loc) { (void)hipFree(b->lseg_loc); b->lseg_loc = nullptr; }
+  if (b->lcount) { (void)hipFree(b->lcount); b->lcount = nullptr; }
+  if (b->h_lc) { (void)hipHostFree(b->h_lc); b->h_lc = nullptr; }
+  if (b->h_count) { (void)hipHostFree(b->h_count); b->h_count = nullptr; }
+  for (hipEvent_t& e : b->lev)
+    if (e) { (void)hipEventDestroy(e); e = nullptr; }
+  b->lap_family = -1;
+}
+
 void batch_free(sgp_batch* b) {
   (void)hipSetDevice(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
@@ -5648,6 +5734,7 @@ void batch_free(sgp_batch* b) {
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : b->fev)
     if (e) (void)hipEventDestroy(e);
+  batch_free_lap(b);
   for (double* p : {b->X, b->y, b->mu, b->par, b->rec1, b->rec2, b->pm, b->sc, b->out, b->post,
                     b->res, b->hk, b->rec3, b->fw, b->rec4})
     if (p) (void)hipFree(p);
@@ -5807,6 +5894,7 @@ int sgp_batch_create(sgp_batch** out, int device, const double* X, int64_t nrows
   b->nsegs.assign((size_t)B, 0);
   b->last_m.assign((size_t)B, 0);
   b->has_state.assign((size_t)B, 0);
+  b->hy.assign(y, y + nrows);
   const int cst = batch_create_impl(b, X, ldx, y, mu);
   if (cst != SGP_OK) {
     const std::string keep = g_err;
@@ -5827,6 +5915,11 @@ int sgp_batch_destroy(sgp_batch* b) {
 int sgp_batch_set_data(sgp_batch* b, const double* y, const double* mu) {
   if (!b) { set_err("sgp_batch_set_data: the sgp_batch is NULL"); return SGP_EINVAL; }
   if (!y || !mu) { set_err("sgp_batch_set_data: y and mu must not be NULL"); return SGP_EINVAL; }
+  if (b->lap_family == SGP_FAM_BERNOULLI) {
+    const int bst = batch_check_bern("sgp_batch_set_data", y, b->row0.data(), b->nrow.data(), b->B);
+    if (bst != SGP_OK) return bst;
+  }
+  b->hy.assign(y, y + b->nrows);
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipMemcpyAsync(b->y, y, sizeof(double) * b->nrows, hipMemcpyHostToDevice, b->stream));
   HIPCHK(hipMemcpyAsync(b->mu, mu, sizeof(double) * b->nrows, hipMemcpyHostToDevice, b->stream));
@@ -5841,17 +5934,14 @@ int sgp_batch_set_data(sgp_batch* b, const double* y, const double* mu) {
 
 namespace {
 
-// sgp_batch_eval_vi (grad_knot = nullptr) and sgp_batch_eval_vi_knots after their checks: the
-// same four launches on the same arguments, and with grad_knot the two knot launches behind them;
-// sgp_batch_eval_fitc (fitc = 1, grad_knot = nullptr): its five launches on the same arguments
-int batch_eval_impl(sgp_batch* b, int fitc, int kernel, const double* theta, int64_t ldt, const double* U,
-                    const int64_t* uoff, const int64_t* m, double delta, unsigned flags,
-                    const unsigned char* active, double* obj, double* grad, int64_t ldg,
-                    int* status, const double* bounds, double* grad_knot) {
-  const int d = b->d, ard = kernel == SGP_KERNEL_ARD, L = ard ? d : 1, P = L + 2;
-  const bool obj_only = flags & SGP_FLAG_OBJ_ONLY;
+// The problems' parameter blocks into h_par (objective: BP_OBJ's value); *gtot: the active
+// problems' m d values.  Returns whether any problem is active.
+bool batch_fill_par(sgp_batch* b, int objective, int kernel, const double* theta, int64_t ldt,
+                    const double* U, const int64_t* uoff, const int64_t* m, double delta,
+                    unsigned flags, const unsigned char* active, int64_t* gtot) {
+  const int d = b->d, ard = kernel == SGP_KERNEL_ARD, L = ard ? d : 1;
   bool any = false;
-  int64_t gtot = 0;   // the packed knot gradients: the active problems' m d values in order
+  *gtot = 0;
   for (int64_t p = 0; p < b->B; ++p) {
     double* h = b->h_par + p * b->pst;
     const bool on = !active || active[p];
@@ -5869,15 +5959,30 @@ int batch_eval_impl(sgp_batch* b, int fitc, int kernel, const double* theta, int
     h[BP_RDET] = (flags & SGP_FLAG_R_DET) ? 1.0 : 0.0;
     h[BP_SEG0] = (double)b->seg0[(size_t)p];
     h[BP_NSEG] = (double)b->nsegs[(size_t)p];
-    h[BP_GOFF] = (double)gtot;
-    h[BP_OBJ] = fitc ? 1.0 : 0.0;
-    gtot += m[p] * d;
+    h[BP_GOFF] = (double)*gtot;
+    h[BP_OBJ] = (double)objective;
+    *gtot += m[p] * d;
     for (int c = 0; c < d; ++c) h[BP_RL + c] = 1.0 / th[1 + (ard ? c : 0)];
     const double* u = U + uoff[p];
     for (int c = 0; c < d; ++c)
       for (int j = 0; j < SGP_BATCH_MMAX; ++j)
         h[BP_U + c * SGP_BATCH_MMAX + j] = j < m[p] ? u[(int64_t)c * m[p] + j] : 0.0;
   }
+  return any;
+}
+
+// sgp_batch_eval_vi (grad_knot = nullptr) and sgp_batch_eval_vi_knots after their checks: the
+// same four launches on the same arguments, and with grad_knot the two knot launches behind them;
+// sgp_batch_eval_fitc (fitc = 1, grad_knot = nullptr): its five launches on the same arguments
+int batch_eval_impl(sgp_batch* b, int fitc, int kernel, const double* theta, int64_t ldt, const double* U,
+                    const int64_t* uoff, const int64_t* m, double delta, unsigned flags,
+                    const unsigned char* active, double* obj, double* grad, int64_t ldg,
+                    int* status, const double* bounds, double* grad_knot) {
+  const int d = b->d, ard = kernel == SGP_KERNEL_ARD, L = ard ? d : 1, P = L + 2;
+  const bool obj_only = flags & SGP_FLAG_OBJ_ONLY;
+  int64_t gtot = 0;   // the packed knot gradients: the active problems' m d values in order
+  const bool any = batch_fill_par(b, fitc ? 1 : 0, kernel, theta, ldt, U, uoff, m, delta, flags,
+                                  active, &gtot);
   if (!any) return SGP_OK;
   const int64_t npar = b->B * b->pst;
   if (grad_knot && bounds) std::copy(bounds, bounds + b->B * 2 * d, b->h_par + npar);
@@ -5981,6 +6086,261 @@ int sgp_diag_batch_fitc_timing(sgp_batch* b, int enable, double* stage_ms) {
   if (stage_ms)
     for (int q = 0; q < 5; ++q) stage_ms[q] = b->ftiming ? (double)b->fstage_ms[q] : 0.0;
   b->ftiming = enable != 0;
+  return SGP_OK;
+}
+
+// ------------------------------------------------------------------------- batched Laplace
+// sgp_batch_lap_* / sgp_batch_eval_laplace (include/sgp.h; k_batch_laplace.hip)
+int sgp_diag_batch_lap_args(const double* y, int64_t nrows, const int64_t* row0,
+                            const int64_t* nrow, int64_t B, int family, const double* expo) {
+  return batch_check_lap(y, nrows, row0, nrow, B, family, expo);
+}
+
+int sgp_batch_lap_init(sgp_batch* b, int family, const double* expo) {
+  if (!b) { set_err("sgp_batch_lap_init: the sgp_batch is NULL"); return SGP_EINVAL; }
+  const int cst = batch_check_lap(b->hy.data(), b->nrows, b->row0.data(), b->nrow.data(), b->B,
+                                  family, expo);
+  if (cst != SGP_OK) return cst;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (b->loff.empty()) {   // the first call allocates; a repeat replaces family, exposure and f
+    std::vector<int64_t> off((size_t)b->B + 1, 0), sl((size_t)b->nseg, 0);
+    for (int64_t p = 0; p < b->B; ++p) {
+      off[(size_t)p + 1] = off[(size_t)p] + b->nrow[(size_t)p];
+      for (int64_t q = 0; q < b->nsegs[(size_t)p]; ++q)
+        sl[(size_t)(b->seg0[(size_t)p] + q)] = off[(size_t)p] + q * SGP_BATCH_SEG_ROWS;
+    }
+    const int64_t tot = off[(size_t)b->B];
+    for (hipEvent_t& e : b->lev) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipMalloc(&b->lexpo, sizeof(double) * b->nrows));
+    HIPCHK(hipMalloc(&b->lf, sizeof(double) * tot));
+    HIPCHK(hipMalloc(&b->lzv, sizeof(double) * tot));
+    HIPCHK(hipMalloc(&b->llw, sizeof(double) * b->B * BATCH_LW));
+    HIPCHK(hipMalloc(&b->llc, sizeof(double) * b->B * BATCH_LC));
+    HIPCHK(hipMalloc(&b->llrec, sizeof(double) * b->nseg * BATCH_LREC));
+    HIPCHK(hipMalloc(&b->lobjs, sizeof(double) * b->B * BATCH_LAP_NOBJ));
+    HIPCHK(hipMalloc(&b->lseg_loc, sizeof(int64_t) * b->nseg));
+    HIPCHK(hipMalloc(&b->lcount, sizeof(int)));
+    HIPCHK(hipHostMalloc(&b->h_lc, sizeof(double) * b->B * BATCH_LC));
+    HIPCHK(hipHostMalloc(&b->h_count, sizeof(int)));
+    HIPCHK(hipMemcpy(b->lseg_loc, sl.data(), sizeof(int64_t) * sl.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(b->llc, 0, sizeof(double) * b->B * BATCH_LC, b->stream));
+    HIPCHK(hipMemsetAsync(b->lobjs, 0, sizeof(double) * b->B * BATCH_LAP_NOBJ, b->stream));
+    b->loff = off;
+  }
+  const int64_t tot = b->loff[(size_t)b->B];
+  if (expo) {
+    HIPCHK(hipMemcpy(b->lexpo, expo, sizeof(double) * b->nrows, hipMemcpyHostToDevice));
+  } else {
+    const std::vector<double> one((size_t)b->nrows, 1.0);
+    HIPCHK(hipMemcpy(b->lexpo, one.data(), sizeof(double) * b->nrows, hipMemcpyHostToDevice));
+  }
+  HIPCHK(hipMemsetAsync(b->lf, 0, sizeof(double) * tot, b->stream));   // f starts at 0
+  HIPCHK(hipStreamSynchronize(b->stream));
+  b->lap_family = family;
+  return SGP_OK;
+}
+
+int sgp_batch_lap_set_f(sgp_batch* b, const double* f, const double* fill) {
+  if (!b) { set_err("sgp_batch_lap_set_f: the sgp_batch is NULL"); return SGP_EINVAL; }
+  if (b->lap_family < 0) {
+    set_err("sgp_batch_lap_set_f: no family set (call sgp_batch_lap_init first)");
+    return SGP_EINVAL;
+  }
+  if (!f && !fill) { set_err("sgp_batch_lap_set_f: f and fill are both NULL"); return SGP_EINVAL; }
+  const int64_t tot = b->loff[(size_t)b->B];
+  int64_t bad = 0;
+  if (!finite_all(f ? f : fill, f ? tot : b->B, &bad)) {
+    set_err("sgp_batch_lap_set_f: %s[%lld] is not finite", f ? "f" : "fill", (long long)bad);
+    return SGP_EINVAL;
+  }
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (f) {
+    HIPCHK(hipMemcpy(b->lf, f, sizeof(double) * tot, hipMemcpyHostToDevice));
+  } else {
+    std::vector<double> h((size_t)tot);
+    for (int64_t p = 0; p < b->B; ++p)
+      std::fill(h.begin() + b->loff[(size_t)p], h.begin() + b->loff[(size_t)p + 1], fill[p]);
+    HIPCHK(hipMemcpy(b->lf, h.data(), sizeof(double) * tot, hipMemcpyHostToDevice));
+  }
+  return SGP_OK;
+}
+
+int sgp_batch_lap_get_f(sgp_batch* b, double* f) {
+  if (!b) { set_err("sgp_batch_lap_get_f: the sgp_batch is NULL"); return SGP_EINVAL; }
+  if (b->lap_family < 0) {
+    set_err("sgp_batch_lap_get_f: no family set (call sgp_batch_lap_init first)");
+    return SGP_EINVAL;
+  }
+  if (!f) { set_err("sgp_batch_lap_get_f: f is NULL"); return SGP_EINVAL; }
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(f, b->lf, sizeof(double) * b->loff[(size_t)b->B], hipMemcpyDeviceToHost));
+  return SGP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// sgp_batch_eval_laplace after its checks.  The per-theta stages and the first objective, then
+// one Newton iteration per turn of the loop over the problems still running: the stop decisions
+// are the device's, and the host reads back their count alone.
+int batch_eval_laplace_impl(sgp_batch* b, int kernel, const double* theta, int64_t ldt,
+                            const double* U, const int64_t* uoff, const int64_t* m, double delta,
+                            unsigned flags, const unsigned char* active, double* obj,
+                            double* grad, int64_t ldg, int* status, double tol, int maxit,
+                            int* nr_iters) {
+  const int d = b->d, ard = kernel == SGP_KERNEL_ARD, L = ard ? d : 1, P = L + 2;
+  const bool obj_only = flags & SGP_FLAG_OBJ_ONLY;
+  int64_t gtot = 0;
+  if (!batch_fill_par(b, 2, kernel, theta, ldt, U, uoff, m, delta, flags, active, &gtot))
+    return SGP_OK;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipMemcpyAsync(b->par, b->h_par, sizeof(double) * b->B * b->pst, hipMemcpyHostToDevice,
+                        b->stream));
+  const BatchArgs a = batch_args(b, ard, obj_only ? 1 : 0);
+  BatchLapArgs l;
+  l.family = b->lap_family; l.maxit = maxit; l.tol = tol;
+  l.expo = b->lap_family == SGP_FAM_POISSON ? b->lexpo : nullptr;   // only Poisson reads it
+  l.seg_loc = b->lseg_loc;
+  l.f = b->lf; l.zv = b->lzv; l.lw = b->llw; l.lc = b->llc; l.lrec = b->llrec;
+  l.objs = b->lobjs; l.count = b->lcount;
+  const bool tm = b->ltiming;
+  if (tm) std::fill(b->lstage_ms, b->lstage_ms + 11, 0.0);
+  // stages[q] runs between events q and q + 1; their times are added to lstage_ms[slot[q]]
+  auto run = [&](const int* stages, const int* slot, int n, bool count) -> int {
+    for (int q = 0; q < n; ++q) {
+      if (tm) HIPCHK(hipEventRecord(b->lev[q], b->stream));
+      HIPCHK(launch_batch_laplace(stages[q], a, l, b->stream));
+    }
+    if (tm) HIPCHK(hipEventRecord(b->lev[n], b->stream));
+    if (count) {
+      HIPCHK(launch_batch_laplace(BL_COUNT, a, l, b->stream));
+      HIPCHK(hipMemcpyAsync(b->h_count, b->lcount, sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    }
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (tm)
+      for (int q = 0; q < n; ++q) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, b->lev[q], b->lev[q + 1]));
+        b->lstage_ms[slot[q]] += (double)ms;
+      }
+    return SGP_OK;
+  };
+  {
+    const int st[5] = {BL_K22, BL_PASSZ, BL_MMZ, BL_OBJ0, BL_MM0}, sl[5] = {0, 1, 2, 3, 4};
+    const int rc = run(st, sl, 5, true);
+    if (rc != SGP_OK) return rc;
+  }
+  for (int it = 0; it < maxit && *b->h_count > 0; ++it) {
+    const int st[4] = {BL_NRA, BL_X2, BL_UPD, BL_MM}, sl[4] = {5, 6, 3, 4};
+    const int rc = run(st, sl, 4, true);
+    if (rc != SGP_OK) return rc;
+  }
+  if (!obj_only) {
+    const int st[4] = {BL_GA, BL_GM, BL_GB, BL_GF}, sl[4] = {7, 8, 9, 10};
+    for (int q = 0; q < 4; ++q) {
+      if (tm) HIPCHK(hipEventRecord(b->lev[q], b->stream));
+      HIPCHK(launch_batch_laplace(st[q], a, l, b->stream));
+    }
+    if (tm) HIPCHK(hipEventRecord(b->lev[4], b->stream));
+    (void)sl;
+  }
+  HIPCHK(hipMemcpyAsync(b->h_out, b->out, sizeof(double) * b->B * BATCH_OUT,
+                        hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipMemcpyAsync(b->h_lc, b->llc, sizeof(double) * b->B * BATCH_LC, hipMemcpyDeviceToHost,
+                        b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (tm && !obj_only)
+    for (int q = 0; q < 4; ++q) {
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, b->lev[q], b->lev[q + 1]));
+      b->lstage_ms[7 + q] = (double)ms;
+    }
+  b->last_ard = ard;
+  bool failed = false;
+  for (int64_t p = 0; p < b->B; ++p) {
+    if (active && !active[p]) continue;
+    const double* o = b->h_out + p * BATCH_OUT;
+    const int st = (int)o[1];
+    status[p] = st;
+    nr_iters[p] = (int)b->h_lc[p * BATCH_LC + LC_IT];
+    if (st) {
+      obj[p] = NAN;
+      if (grad)
+        for (int q = 0; q < P; ++q) grad[p * ldg + q] = NAN;
+      if (!failed)
+        set_err("problem %lld: chol(): the leading minor of order %d of %s is not positive definite",
+                (long long)p, st > 0 ? st : -st,
+                st > 0 ? "Sigma22" : "Sigma22 + t(Sigma12) %*% ZSig12 (or B * Sigma12)");
+      failed = true;
+      continue;
+    }
+    obj[p] = o[0];
+    if (!obj_only)
+      for (int q = 0; q < P; ++q) grad[p * ldg + q] = o[2 + q];
+    b->has_state[(size_t)p] = 1;
+    b->last_m[(size_t)p] = m[p];
+  }
+  return SGP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sgp_batch_eval_laplace(sgp_batch* b, int kernel, const double* theta, int64_t ldt,
+                           const double* U, const int64_t* uoff, const int64_t* m, double delta,
+                           unsigned flags, const unsigned char* active, double* obj, double* grad,
+                           int64_t ldg, int* status, double tol, int maxit, int* nr_iters) {
+  if (!b) { set_err("sgp_batch_eval_laplace: the sgp_batch is NULL"); return SGP_EINVAL; }
+  int cst = batch_check_eval(b->d, b->B, kernel, theta, ldt, U, uoff, m, delta, flags, active,
+                             obj, grad, ldg, status);
+  if (cst != SGP_OK) return cst;
+  cst = batch_check_lap_eval(b->lap_family, tol, maxit, nr_iters);
+  if (cst != SGP_OK) return cst;
+  return batch_eval_laplace_impl(b, kernel, theta, ldt, U, uoff, m, delta, flags, active, obj,
+                                 grad, ldg, status, tol, maxit, nr_iters);
+}
+
+int sgp_diag_batch_lap_eval_args(int family, double tol, int maxit, const int* nr_iters) {
+  return batch_check_lap_eval(family, tol, maxit, nr_iters);
+}
+
+/* The Newton iteration's objective values of problem `prob` in the last sgp_batch_eval_laplace
+ * that evaluated it (newtrap_sparseGP's objective_function_values): *count = nr_iters, of which
+ * the first min(*count, max_n, SGP_BATCH_LAP_NOBJ) are written to out. */
+int sgp_diag_batch_lap_objective_values(sgp_batch* b, int64_t prob, double* out, int max_n,
+                                        int* count) {
+  if (!b) { set_err("sgp_diag_batch_lap_objective_values: the sgp_batch is NULL"); return SGP_EINVAL; }
+  if (b->lap_family < 0 || prob < 0 || prob >= b->B || !out || max_n < 0 || !count) {
+    set_err("sgp_diag_batch_lap_objective_values: prob=%lld of %lld, max_n=%d (and "
+            "sgp_batch_lap_init first)", (long long)prob, (long long)b->B, max_n);
+    return SGP_EINVAL;
+  }
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  double lc[BATCH_LC];
+  HIPCHK(hipMemcpy(lc, b->llc + prob * BATCH_LC, sizeof(lc), hipMemcpyDeviceToHost));
+  *count = (int)lc[LC_IT];
+  const int n = std::min(std::min(*count, max_n), BATCH_LAP_NOBJ);
+  if (n > 0)
+    HIPCHK(hipMemcpy(out, b->lobjs + prob * BATCH_LAP_NOBJ, sizeof(double) * n,
+                     hipMemcpyDeviceToHost));
+  return SGP_OK;
+}
+
+/* stage_ms (11 doubles, or NULL): the HIP-event times of the last sgp_batch_eval_laplace: K22's
+ * stage, the Z pass, the (K22 + S_Z) stage | summed over the Newton iterations: the objective
+ * pass, the C stage, NR's part a, x2 | the gradient's part a, its vector stage, part b, the G22
+ * stage (zero under SGP_FLAG_OBJ_ONLY); enable != 0 records them from the next such call on. */
+int sgp_diag_batch_laplace_timing(sgp_batch* b, int enable, double* stage_ms) {
+  if (!b) { set_err("sgp_diag_batch_laplace_timing: the sgp_batch is NULL"); return SGP_EINVAL; }
+  if (stage_ms)
+    for (int q = 0; q < 11; ++q) stage_ms[q] = b->ltiming ? b->lstage_ms[q] : 0.0;
+  b->ltiming = enable != 0;
   return SGP_OK;
 }
 

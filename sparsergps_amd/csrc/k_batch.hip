@@ -27,6 +27,9 @@
 // k_batch_fitc.hip; it leaves Bm^-1, u and the parameter block in `post` as k_batch_mm does, with
 // the objective at BP_OBJ, so k_batch_post serves it unchanged and k_batch_pred_mm only chooses
 // predict_laplace's constant (no delta) for it.  sgp_batch_dev.h holds the helpers both files use.
+// The Laplace evaluation (sgp_batch_eval_laplace) is k_batch_laplace.hip; it leaves
+// (K22 + S_B)^-1 and x1 there with BP_OBJ = 2, for which k_batch_post and k_batch_pred_mm put
+// tau^2 + delta on K22's diagonal.
 #include <math.h>
 
 #include "sgp_internal.h"
@@ -516,7 +519,9 @@ __global__ void __launch_bounds__(256) k_batch_post(BatchArgs a, double* __restr
   const double* P = post + MM * MM + MM;
   if (P[BP_ACTIVE] == 0.0) return;   // no successful evaluation yet (the state starts zeroed)
   const int d = a.d, m = (int)P[BP_M];
-  const double sig2 = P[BP_SIG2], delta = P[BP_DELTA];
+  const double sig2 = P[BP_SIG2];
+  // K22's diagonal: delta, and tau^2 + delta where the evaluation was a Laplace one (quirk Q1)
+  const double delta = P[BP_OBJ] == 2.0 ? P[BP_TAU2] + P[BP_DELTA] : P[BP_DELTA];
   for (int e = tid; e < m * MM; e += 256) {
     const int i = e >> 6, j = e & (MM - 1);
     if (j >= m) continue;
@@ -566,10 +571,12 @@ __global__ void __launch_bounds__(256) k_batch_pred_mm(BatchArgs a, BatchPredArg
   if (P[BP_ACTIVE] == 0.0) return;   // no successful evaluation (the host refuses this before)
   const int d = a.d, m = (int)P[BP_M];
   const double sig2 = P[BP_SIG2], tau2 = P[BP_TAU2], delta = P[BP_DELTA];
+  // predict_laplace(family != "gaussian") keeps tau^2 on Sigma22's diagonal (sec. 0s)
+  const double dg = P[BP_OBJ] == 2.0 ? tau2 + delta : delta;
   for (int e = tid; e < m * MM; e += 256) {
     const int i = e >> 6, j = e & (MM - 1);
     if (j >= m) continue;
-    A[i * MM + j] = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j)) + (i == j ? delta : 0.0);
+    A[i * MM + j] = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j)) + (i == j ? dg : 0.0);
   }
   double ld22 = 0.0;
   const int st = sweep_spd(A, m, ck, &ld22);

@@ -1,6 +1,6 @@
-// Device helpers shared by the batch kernels (k_batch.hip, k_batch_fitc.hip): the fixed-order
-// sums, the sweep operator of the m x m stages and the knot distances.  Internal linkage: each
-// translation unit compiles its own copy.
+// Device helpers shared by the batch kernels (k_batch.hip, k_batch_fitc.hip,
+// k_batch_laplace.hip): the fixed-order sums, the sweep operator of the m x m stages and the knot
+// distances.  Internal linkage: each translation unit compiles its own copy.
 #pragma once
 #include <math.h>
 

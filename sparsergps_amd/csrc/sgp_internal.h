@@ -609,7 +609,8 @@ hipError_t launch_rec_gather(const RecPass2& p2, const GatherSegs& g, double* ds
 enum {
   BP_M = 0, BP_ACTIVE, BP_SIG2, BP_TAU2, BP_Z, BP_DELTA, BP_NROW, BP_RDET, BP_SEG0, BP_NSEG,
   BP_GOFF,                      // sgp_batch_eval_vi_knots: the problem's offset in the packed result
-  BP_OBJ,                       // the objective the evaluation ran: 0 Titsias VI, 1 FITC (sec. 0q)
+  BP_OBJ,                       // the objective the evaluation ran: 0 Titsias VI, 1 FITC (sec. 0q),
+                                // 2 Laplace (sec. 0s)
   BP_RL = 16,                   // 1 / l_c, d values ("sqexp": 1 / l in each)
   BP_U = 48                     // knots [c][64], zero beyond m
 };
@@ -663,6 +664,37 @@ hipError_t launch_batch_post(const BatchArgs& a, double* res, hipStream_t s);
 // after launch_batch_eval with a.hk set; ev (or nullptr): 3 events recorded before the knot pass,
 // the knot finish and after
 hipError_t launch_batch_knots(const BatchArgs& a, hipStream_t s, hipEvent_t* ev);
+
+// Batched Laplace (sgp_batch_eval_laplace; k_batch_laplace.hip) on the same
+// batch.  BP_OBJ = 2 in the parameter block.  The latent vectors f and Z are indexed by (problem,
+// local row): problem b's rows start at its offset in the packed vectors, segment s's at seg_loc[s].
+// A problem's work slot (row stride 64 in every matrix): K22^-1 | K22 + S_Z | its inverse |
+// K22 + S_B | two slots of C = (K22 + S_B)^-1 used in turn, so the previous iterate's stays
+// (newtrap_sparseGP's u posterior reads it) | x1, x2, s, GG, C w | log|K22|.
+// Its control block: LC_RUN (the Newton iteration goes on), LC_IT (objective values so far),
+// LC_OBJ (the last one).  The vector record of a segment: three m-vectors | max |grad psi|.
+constexpr int LW_A = 0, LW_BZ = BR_T, LW_BZI = 2 * BR_T, LW_BB = 3 * BR_T, LW_C = 4 * BR_T,
+              LW_X1 = 6 * BR_T, LW_X2 = LW_X1 + SGP_BATCH_MMAX, LW_S = LW_X2 + SGP_BATCH_MMAX,
+              LW_GG = LW_S + SGP_BATCH_MMAX, LW_CW = LW_GG + SGP_BATCH_MMAX,
+              LW_LD = LW_CW + SGP_BATCH_MMAX, BATCH_LW = LW_LD + 8;
+enum { LC_RUN = 0, LC_IT, LC_OBJ, BATCH_LC = 4 };
+constexpr int LR_GMAX = 3 * SGP_BATCH_MMAX, BATCH_LREC = LR_GMAX + 8;
+constexpr int BATCH_LAP_NOBJ = 256;      // include/sgp_diag.h: SGP_BATCH_LAP_NOBJ
+struct BatchLapArgs {
+  int family, maxit;
+  double tol;
+  const double* expo;           // the resident rows' exposure, or nullptr (1 on every row)
+  const int64_t* seg_loc;       // per segment: its first row in the packed latent vectors
+  double *f, *zv;               // packed by problem: the latent f and Z_i
+  double *lw, *lc, *lrec;       // B work slots, B control blocks, nseg vector records
+  double* objs;                 // B x BATCH_LAP_NOBJ: the Newton iteration's objective values
+  int* count;                   // the problems whose Newton iteration goes on
+};
+// The stages of one evaluation; the caller orders them (capi.hip: batch_eval_laplace_impl).
+enum { BL_K22 = 0, BL_PASSZ, BL_MMZ, BL_OBJ0, BL_MM0, BL_NRA, BL_X2, BL_UPD, BL_MM, BL_COUNT,
+       BL_GA, BL_GM, BL_GB, BL_GF };
+hipError_t launch_batch_laplace(int stage, const BatchArgs& a, const BatchLapArgs& l,
+                                hipStream_t s);
 
 // Batched held-out prediction and scoring (sgp_batch_predict) from the state
 // `post` holds.  A problem's work slot: T = Bm^-1 - K22^-1 (row stride 64) | c0 = (tau^2 +
