@@ -297,7 +297,12 @@ int sgp_full_laplace_state(sgp_ctx* ctx, double* W, double* grad_log_py_ff);
 /* Posterior of the knot values u at the end of a fit, from the context's last completed
  * evaluation (VI: vi_functions.R:1161-1180; FITC: laplace_gradient_ascent.R:1635-1655;
  * Laplace: newtrap_sparseGP.R:137-176).  muu, u_mean: m host values; u_var: m x m host,
- * column-major (ld m). */
+ * column-major (ld m).
+ * "Completed" is exact: an evaluation forgets its predecessor when it starts (it overwrites
+ * m, the knots and the m x m state this reads) and counts only once it has returned SGP_OK.
+ * After an evaluation that failed (SGP_ENOTPD included), after any of the three candidate
+ * scorers below, and on a new context, this returns SGP_EINVAL ("no completed evaluation");
+ * sgp_knot_gradient follows the same rule.  Evaluate again to ask again. */
 int sgp_posterior_u(sgp_ctx* ctx, const double* muu, double* u_mean, double* u_var);
 
 /* Sparse prediction at x_pred (np x d, column-major, ld ldxp) from a knot posterior:
@@ -718,14 +723,20 @@ int sgp_ctx_row_bounds(sgp_ctx* ctx, double* col_min, double* col_max);
  * (cand: T x d, column-major, ld ldc) at fixed theta -- the meta-model y values of
  * knot_prop_random_norm_vi / knot_prop_ego_norm_vi (R/vi_functions.R:2196-2300, 1584-) --
  * from bordered Schur complements instead of T rebuilds of K12.  NaN marks a candidate whose
- * bordered K22 or Bm is not positive definite (the reference's try-error). */
+ * bordered K22 or Bm is not positive definite (the reference's try-error).  m <= m_max is
+ * enough on one device (nothing is built at m + 1; a row-sharded context rebuilds and needs
+ * m + 1 <= m_max).  Afterwards the context holds the base system at (theta, U) without its
+ * second phase, which is no completed evaluation: sgp_posterior_u and sgp_knot_gradient
+ * refuse until the next evaluation, also when (theta, U) are those of the evaluation before. */
 int sgp_vi_candidates(sgp_ctx* ctx, int kernel, const double* theta, const double* U, int64_t m,
                       int64_t ldu, double delta, unsigned flags, const double* cand, int64_t T,
                       int64_t ldc, double* obj_out);
 
 /* OAT knot proposal scoring for FITC (knot_prop_random_norm / knot_prop_ego_norm,
  * R/knot_proposal_functions.R:1176-1363, 498-): obj_fun_norm at knots [U; cand_t] with
- * Sigma22 = Kuu + delta I, for each of T candidates (m + 1 <= m_max).  NaN = try-error. */
+ * Sigma22 = Kuu + delta I, for each of T candidates (m + 1 <= m_max).  NaN = try-error; the
+ * candidates after it are scored as usual.  Afterwards the context's state is the last
+ * candidate's: sgp_posterior_u and sgp_knot_gradient refuse until the next evaluation. */
 int sgp_fitc_candidates(sgp_ctx* ctx, int kernel, const double* theta, const double* U,
                         int64_t m, int64_t ldu, double delta, unsigned flags, const double* cand,
                         int64_t T, int64_t ldc, double* obj_out);
@@ -733,7 +744,9 @@ int sgp_fitc_candidates(sgp_ctx* ctx, int kernel, const double* theta, const dou
 /* OAT knot proposal scoring for Poisson Laplace (knot_prop_random / knot_prop_ego,
  * R/knot_proposal_functions.R:1001-1173, 46-): for each candidate, newtrap_sparseGP at knots
  * [U; cand_t] warm-started from the resident f (the fit's fmax); obj_out[t] = its last
- * objective value.  The resident f is restored afterwards.  NaN = try-error. */
+ * objective value.  The resident f is restored afterwards, also past a try-error (NaN).
+ * sgp_posterior_u, sgp_knot_gradient and sgp_lap_get_grad_psi refuse until the next
+ * evaluation. */
 int sgp_lap_candidates(sgp_ctx* ctx, int kernel, const double* theta, const double* U, int64_t m,
                        int64_t ldu, double delta, double expo, double tol, int maxit,
                        const double* cand, int64_t T, int64_t ldc, double* obj_out);

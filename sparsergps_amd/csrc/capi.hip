@@ -672,11 +672,20 @@ int check_eval_args(sgp_ctx* c, int kernel, const double* theta, const double* U
 
 }  // namespace
 
+// An evaluation (or a scorer's base) is about to overwrite m, the knots and the m x m state that
+// sgp_posterior_u and sgp_knot_gradient read: from here until an evaluation's finish sets
+// last_mode again there is no completed evaluation to answer for, whether this one succeeds,
+// fails (SGP_ENOTPD) or, as in sgp_vi_candidates, never finishes at all.
+static void forget_posterior(sgp_ctx* c) {
+  c->last_mode = 0;
+  c->knot_raw.clear();
+}
+
 // multi.hip's hooks (sgp_multi.h)
 void sgp_internal_set_err(const char* msg) { set_err("%s", msg); }
 
 void sgp_internal_forget_eval(sgp_ctx* c) {
-  c->last_mode = 0;
+  forget_posterior(c);
   c->lap_gpsi_valid = false;
   c->fl_valid = false;
 }
@@ -1290,7 +1299,8 @@ int sgp_knot_gradient(sgp_ctx* c, const double* bounds, double* grad_knot) {
   MULTI_FWD(c, grad_knot ? multi_knot_gradient(c->multi, bounds, grad_knot) : multi_bad_args());
   if (!c || !grad_knot) { set_err("invalid arguments"); return SGP_EINVAL; }
   const int64_t m = c->m, d = c->d;
-  if (c->knot_raw.size() != (size_t)(m * d) || c->last_mode == 0) {
+  if (c->last_mode == 0) { set_err("no completed evaluation in this context"); return SGP_EINVAL; }
+  if (c->knot_raw.size() != (size_t)(m * d)) {
     set_err("no knot gradient: enable it with sgp_ctx_enable_knot_grad before the evaluation");
     return SGP_EINVAL;
   }
@@ -1343,6 +1353,7 @@ int sgp_vi_phase1(sgp_ctx* c, int kernel, const double* theta, const double* U, 
   st = drain_abandoned(c);
   if (st) return st;
   timers_reset(c);
+  forget_posterior(c);
   c->kp = kp;
   c->m = m;
   c->mp = round_up(m, SGP_TILE);
@@ -1776,6 +1787,7 @@ int sgp_fitc_phase1(sgp_ctx* c, int kernel, const double* theta, const double* U
   st = drain_abandoned(c);
   if (st) return st;
   timers_reset(c);
+  forget_posterior(c);
   c->kp = kp;
   c->m = m;
   c->mp = round_up(m, SGP_TILE);
@@ -2191,6 +2203,7 @@ int sgp_lap_begin(sgp_ctx* c, int kernel, const double* theta, const double* U, 
   st = lap_ensure(c);
   if (st) return st;
   timers_reset(c);
+  forget_posterior(c);
   c->kp = kp;
   c->m = m;
   c->mp = round_up(m, SGP_TILE);
@@ -2626,8 +2639,7 @@ int sgp_eval_full(sgp_ctx* c, int kernel, const double* theta, double delta, uns
   c->delta = delta;
   c->flags = flags;
   c->phase = 0;
-  c->last_mode = 0;
-  c->knot_raw.clear();
+  forget_posterior(c);
   const int64_t mp = c->mp, mm = mp * mp;
   // the rows are the "knots": X (ld n_pad) -> U (ld mp), zero padded alike (mp == n_pad)
   HIPCHK(hipMemcpy2DAsync(c->U, sizeof(double) * mp, c->X, sizeof(double) * c->n_pad,
@@ -2805,8 +2817,7 @@ int sgp_eval_full_laplace(sgp_ctx* c, int kernel, const double* theta, double de
   c->delta = delta;
   c->flags = flags;
   c->phase = 0;
-  c->last_mode = 0;
-  c->knot_raw.clear();
+  forget_posterior(c);
   c->lap_state = LS_NONE;
   c->lap_expo = expo == SGP_EXPO_ROWS ? 1.0 : expo;
   c->lap_av = expo == SGP_EXPO_ROWS ? lvec(c, LV_AEXP) : nullptr;
@@ -4976,6 +4987,9 @@ int sgp_vi_candidates(sgp_ctx* c, int kernel, const double* theta, const double*
       obj_out[t0 + j] = qd + det_part - (n / 2.0) * log(2.0 * M_PI) + tt;
     }
   }
+  // as the FITC and Laplace scorers: phase 1 above forgot the evaluation before this call, and
+  // the base state it left (no phase 2, no finish) is no completed evaluation either
+  forget_posterior(c);
   return SGP_OK;
 }
 
@@ -5019,7 +5033,7 @@ int sgp_fitc_candidates(sgp_ctx* c, int kernel, const double* theta, const doubl
     if (st) return st;
     obj_out[t] = o;
   }
-  c->last_mode = 0;   // the context's posterior state belongs to the last candidate
+  forget_posterior(c);   // the context's posterior state belongs to the last candidate
   return SGP_OK;
 }
 
@@ -5065,7 +5079,7 @@ int sgp_lap_candidates(sgp_ctx* c, int kernel, const double* theta, const double
   HIPCHK(hipMemcpyAsync(lvec(c, LV_F), f0.p, sizeof(double) * c->n_pad, hipMemcpyDeviceToDevice,
                         c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  c->last_mode = 0;   // the context's posterior state belongs to the last candidate
+  forget_posterior(c);   // the context's posterior state belongs to the last candidate
   c->lap_gpsi_valid = false;
   return st;
 }
