@@ -26,10 +26,15 @@
 // The FITC evaluation of the same batch (sgp_batch_eval_fitc) is
 // k_batch_fitc.hip; it leaves Bm^-1, u and the parameter block in `post` as k_batch_mm does, with
 // the objective at BP_OBJ, so k_batch_post serves it unchanged and k_batch_pred_mm only chooses
-// predict_laplace's constant (no delta) for it.  sgp_batch_dev.h holds the helpers both files use.
+// predict_laplace's constant (no delta) for it.
 // The Laplace evaluation (sgp_batch_eval_laplace) is k_batch_laplace.hip; it leaves
 // (K22 + S_B)^-1 and x1 there with BP_OBJ = 2, for which k_batch_post and k_batch_pred_mm put
 // tau^2 + delta on K22's diagonal.
+// sgp_batch_dev.h holds what the three files share: the fixed-order sums, the NT dispatch, the
+// pieces of the m x m stages (for_mm, the sweep, Kuu, the sandwich's first half, the contraction
+// of H, the posterior store) and of the row passes in pass 2's layout (the staging, rows_k, kmat,
+// row_dot, k_dot, store_pairs).  Pass 1's knot-major k, pass 2's per-thread ARD slots and its
+// coincidence counts, the prediction's statistics and the knot pass are this file's own.
 #include <math.h>
 
 #include "sgp_internal.h"
@@ -67,11 +72,7 @@ __device__ __forceinline__ void pass1_body(const BatchArgs& a, const double* __r
 
   for (int step = 0; step * 64 < rows; ++step) {
     __syncthreads();   // the staging above / the previous step's reads of xs and rs
-    for (int q = tid; q < d * 64; q += 256) {
-      const int c = q >> 6, i = q & 63;
-      const int row = step * 64 + i;
-      xs[q] = row < rows ? a.X[(int64_t)c * a.ldx + row0 + row] : 0.0;
-    }
+    stage_x(a.X, a.ldx, row0, rows, step, d, xs);
     if (tid < 64) {
       const int row = step * 64 + tid;
       const double r = row < rows ? a.y[row0 + row] - a.mu[row0 + row] : 0.0;
@@ -124,36 +125,12 @@ __device__ __forceinline__ void pass1_body(const BatchArgs& a, const double* __r
     }
   }
 
-  // the four waves' partial S, added in wave order into LDS (over the dead knots and rows)
-  for (int w = 0; w < 4; ++w) {
-    __syncthreads();
-    if (wv == w) {
-      int p = 0;
-#pragma unroll
-      for (int bi = 0; bi < NT; ++bi)
-#pragma unroll
-        for (int bj = bi; bj < NT; ++bj, ++p)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            double* s = lds + (16 * bi + 4 * r + g) * MM + 16 * bj + r16;
-            *s = w ? *s + acc[p][r] : acc[p][r];
-          }
-    }
-  }
-#pragma unroll
-  for (int b = 0; b < NT; ++b) {
-    double t = tacc[b];
-    t += __shfl_xor(t, 16, 64);
-    t += __shfl_xor(t, 32, 64);
-    if (g == 0) tw[wv * MM + 16 * b + r16] = t;
-  }
+  // tw and rrs are arrays of their own, written before store_pairs so that its last barrier
+  // serves them too; S goes over the dead knots and rows
+  fold_tacc<NT>(tacc, tw);
   if (tid < 64) rrs[tid] = rracc;
-  __syncthreads();
-  for (int q = tid; q < Mp * Mp; q += 256) {
-    const int i = q / Mp, j = q - i * Mp;
-    rec[i * MM + j] = (i >> 4) > (j >> 4) ? lds[j * MM + i] : lds[i * MM + j];
-  }
-  if (tid < Mp) rec[BR_T + tid] = ((tw[tid] + tw[MM + tid]) + tw[2 * MM + tid]) + tw[3 * MM + tid];
+  store_pairs<NT>(acc, lds, rec);
+  if (tid < Mp) rec[BR_T + tid] = wave_sum4(tw, tid);
   if (tid == 0) {
     double rr = 0.0;
     for (int q = 0; q < 64; ++q) rr += rrs[q];
@@ -171,12 +148,7 @@ __global__ void __launch_bounds__(256) k_batch_pass1(BatchArgs a) {
   const int64_t row0 = a.seg_row0[seg];
   const int rows = a.seg_rows[seg];
   double* rec = a.rec1 + (int64_t)seg * BATCH_REC1;
-  switch (((int)P[BP_M] + 15) >> 4) {
-    case 1: pass1_body<1>(a, P, row0, rows, rec, lds, tw, rrs, rl_s); break;
-    case 2: pass1_body<2>(a, P, row0, rows, rec, lds, tw, rrs, rl_s); break;
-    case 3: pass1_body<3>(a, P, row0, rows, rec, lds, tw, rrs, rl_s); break;
-    default: pass1_body<4>(a, P, row0, rows, rec, lds, tw, rrs, rl_s); break;
-  }
+  SGP_BATCH_NT(P[BP_M], pass1_body<NT>(a, P, row0, rows, rec, lds, tw, rrs, rl_s))
 }
 
 // ------------------------------------------------------------------------------ m x m stage
@@ -194,16 +166,13 @@ __global__ void __launch_bounds__(256) k_batch_mm(BatchArgs a) {
   double* sc = a.sc + (int64_t)prob * BATCH_SC;
 
   // the segment records, in segment order
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
+  for_mm(m, [&](int i, int j) {
     const double s = rec_sum(a.rec1 + (int64_t)seg0 * BATCH_REC1 + i * MM + j, BATCH_REC1, nseg);
     S[i * MM + j] = s;
-    const double kuu = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j));
-    const double k22 = kuu + (i == j ? delta : 0.0);
-    A[i * MM + j] = k22;
-    Bm[i * MM + j] = k22 + s / z;
-  }
+    const double kd = k22(P, d, i, j, sig2, delta);
+    A[i * MM + j] = kd;
+    Bm[i * MM + j] = kd + s / z;
+  });
   if (tid < m) t_s[tid] = rec_sum(a.rec1 + (int64_t)seg0 * BATCH_REC1 + BR_T + tid, BATCH_REC1, nseg);
   const double rr = rec_sum(a.rec1 + (int64_t)seg0 * BATCH_REC1 + BR_RR, BATCH_REC1, nseg);
 
@@ -218,24 +187,16 @@ __global__ void __launch_bounds__(256) k_batch_mm(BatchArgs a) {
     return;
   }
   // A = K22^-1, Bm = Bm^-1
-  if (tid < m) {
-    double s = 0.0;
-    for (int k = 0; k < m; ++k) s = fma(Bm[tid * MM + k], t_s[k], s);
-    u_s[tid] = s / z;
-  }
+  if (tid < m) u_s[tid] = mat_vec_row(Bm, t_s, tid, m) / z;
   __syncthreads();
-  double su = 0.0;
-  if (tid < m)
-    for (int k = 0; k < m; ++k) su = fma(S[tid * MM + k], u_s[k], su);
+  const double su = tid < m ? mat_vec_row(S, u_s, tid, m) : 0.0;
   const double tu = block_sum(tid < m ? t_s[tid] * u_s[tid] : 0.0, red);
   const double uSu = block_sum(tid < m ? u_s[tid] * su : 0.0, red);
   double p1 = 0.0, p2 = 0.0;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
+  for_mm(m, [&](int i, int j) {
     p1 = fma(A[i * MM + j], S[i * MM + j], p1);
     p2 = fma(Bm[i * MM + j], S[i * MM + j], p2);
-  }
+  });
   const double trKS = block_sum(p1, red);
   const double trBS = block_sum(p2, red);
 
@@ -252,79 +213,32 @@ __global__ void __launch_bounds__(256) k_batch_mm(BatchArgs a) {
     sc[BS_ATA] = (rr - 2.0 * tu + uSu) / (z * z);
   }
   // what sgp_batch_posterior_u needs: Bm^-1, u and the problem's parameters and knots
-  double* post = a.post + (int64_t)prob * a.post_stride;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    post[i * MM + j] = Bm[i * MM + j];
-  }
-  if (tid < m) post[MM * MM + tid] = u_s[tid];
-  for (int q = tid; q < a.pst; q += 256) post[MM * MM + MM + q] = P[q];
+  store_post(a, prob, P, Bm, u_s, m);
   if (a.obj_only) return;
 
   double* pm = a.pm + (int64_t)prob * BATCH_PM;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
+  for_mm(m, [&](int i, int j) {
     pm[i * MM + j] = A[i * MM + j] / tau2 - Bm[i * MM + j] / z - u_s[i] * u_s[j] / z;
-  }
+  });
   if (tid < m) {
     pm[BPM_U + tid] = u_s[tid];
     pm[BPM_KD + tid] = A[tid * MM + tid];
   }
   // G22 = -1/2 u u^T + 1/2 (K22^-1 - Bm^-1) - K22^-1 S K22^-1 / (2 tau^2), contracted with
-  // dK22 / dlog theta (sigma: 2 Kuu; l: Kuu |D|^2 / l^2; l_c: Kuu (D_c / l_c)^2; tau: none)
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    double s = 0.0;
-    for (int k = 0; k < m; ++k) s = fma(A[i * MM + k], S[k * MM + j], s);
-    T[i * MM + j] = s;
-  }
-  __syncthreads();
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    double s = 0.0;
-    for (int k = 0; k < m; ++k) s = fma(T[i * MM + k], A[k * MM + j], s);
+  // dK22 / dlog theta (contract_h; tau: none)
+  sandwich(A, S, T, m);
+  for_mm(m, [&](int i, int j) {
+    const double s = dot_mm(T, A, i, j, m);
     const double g22 = -0.5 * u_s[i] * u_s[j] + 0.5 * (A[i * MM + j] - Bm[i * MM + j]) -
                        s / (2.0 * tau2);
-    const double kuu = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j));
-    Bm[i * MM + j] = g22 * kuu;   // H: each thread rewrites only the entries it read
-  }
+    Bm[i * MM + j] = g22 * kuu(P, d, i, j, sig2);   // H: a thread rewrites only what it read
+  });
   __syncthreads();
   if (a.hk) {   // sgp_batch_eval_vi_knots only: k_batch_knot_finish contracts H with the knots
     double* hk = a.hk + (int64_t)prob * BR_T;
-    for (int e = tid; e < m * MM; e += 256)
-      if ((e & (MM - 1)) < m) hk[e] = Bm[e];
+    for_mm(m, [&](int i, int j) { hk[i * MM + j] = Bm[i * MM + j]; });
   }
-  double h = 0.0;
-  for (int e = tid; e < m * MM; e += 256)
-    if ((e & (MM - 1)) < m) h += Bm[e];
-  const double hs = block_sum(h, red);
-  if (tid == 0) sc[BS_G22] = 2.0 * hs;
-  if (a.ard) {
-    for (int c = 0; c < d; ++c) {
-      double v = 0.0;
-      for (int e = tid; e < m * MM; e += 256) {
-        const int i = e >> 6, j = e & (MM - 1);
-        if (j >= m) continue;
-        const double t = (P[BP_U + c * MM + i] - P[BP_U + c * MM + j]) * P[BP_RL + c];
-        v = fma(Bm[i * MM + j], t * t, v);
-      }
-      const double vs = block_sum(v, red);
-      if (tid == 0) sc[BS_G22 + 1 + c] = vs;
-    }
-  } else {
-    double v = 0.0;
-    for (int e = tid; e < m * MM; e += 256) {
-      const int i = e >> 6, j = e & (MM - 1);
-      if (j >= m) continue;
-      v = fma(Bm[i * MM + j], knot_dist2(P, d, i, j), v);
-    }
-    const double vs = block_sum(v, red);
-    if (tid == 0) sc[BS_G22 + 1] = vs;
-  }
+  contract_h(P, d, m, a.ard, Bm, red, sc + BS_G22);
 }
 
 // ------------------------------------------------------------------------------ row pass 2
@@ -342,64 +256,28 @@ __device__ __forceinline__ void pass2_body(const BatchArgs& a, const double* __r
   double* rl_s = vec_s + 3 * MM;   // d
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, g = lane >> 4;
 
-  for (int q = tid; q < d * Mp; q += 256) {
-    const int c = q / Mp, j = q - c * Mp;
-    xu_s[(c * 4 + (j & 3)) * SN + (j >> 2)] = P[BP_U + c * MM + j];
-  }
-  for (int q = tid; q < Mp * Mp; q += 256) {
-    const int i = q / Mp, j = q - i * Mp;
-    pp_s[q] = (i < m && j < m) ? pm[i * MM + j] : 0.0;
-  }
-  for (int q = tid; q < Mp; q += 256) {
-    u_s[(q & 3) * SN + (q >> 2)] = q < m ? pm[BPM_U + q] : 0.0;
-    kd_s[(q & 3) * SN + (q >> 2)] = q < m ? pm[BPM_KD + q] : 0.0;
-  }
-  for (int q = tid; q < d; q += 256) rl_s[q] = P[BP_RL + q];
+  stage_knots(P, d, Mp, SN, xu_s, rl_s);
+  stage_mat(pm, m, Mp, pp_s);
+  stage_vec(pm + BPM_U, m, Mp, SN, u_s);
+  stage_vec(pm + BPM_KD, m, Mp, SN, kd_s);
   if (ARD)
     for (int c = 0; c < d; ++c) el_s[c * 256 + tid] = 0.0;
 
   double esig = 0.0, el = 0.0, csum = 0.0, ccnt = 0.0, cdg = 0.0;
   for (int step = 0; step * 64 < rows; ++step) {
     __syncthreads();
-    for (int q = tid; q < d * 64; q += 256) {
-      const int c = q >> 6, i = q & 63;
-      const int row = step * 64 + i;
-      xs[q] = row < rows ? a.X[(int64_t)c * a.ldx + row0 + row] : 0.0;
-    }
+    stage_x(a.X, a.ldx, row0, rows, step, d, xs);
     if (tid < 64) {
       const int row = step * 64 + tid;
       rs[tid] = row < rows ? (a.y[row0 + row] - a.mu[row0 + row]) * rz : 0.0;
     }
     __syncthreads();
 
-    const bool iv = step * 64 + wv * 16 + r16 < rows;
-    const double* xr = xs + wv * 16 + r16;
     double e2[SN], kf[SN];
-#pragma unroll
-    for (int s = 0; s < SN; ++s) e2[s] = 0.0;
-    for (int c = 0; c < d; ++c) {
-      const double xc = xr[c * 64], rl = rl_s[c];
-      const double* u = xu_s + (c * 4 + g) * SN;
-#pragma unroll
-      for (int s = 0; s < SN; ++s) {
-        const double t = (xc - u[s]) * rl;   // the raw difference first: coincidence stays exact
-        e2[s] = fma(t, t, e2[s]);
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < SN; ++s) {
-      const double v = sig2 * sgp_exp_nonpos(-0.5 * e2[s]);
-      kf[s] = (iv && 4 * s + g < m) ? v : 0.0;
-    }
+    const bool iv = rows_k<SN>(xs, xu_s, rl_s, d, m, sig2, rows, step, e2, kf);
+    const double* xr = xs + wv * 16 + r16;
     d4 acc[NT];
-#pragma unroll
-    for (int cb = 0; cb < NT; ++cb) acc[cb] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < SN; ++s)
-#pragma unroll
-      for (int cb = 0; cb < NT; ++cb)
-        acc[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(pp_s[(4 * s + g) * Mp + 16 * cb + r16],
-                                                       kf[s], acc[cb], 0, 0, 0);
+    kmat<NT>(pp_s, kf, acc);
     const double ri = rs[wv * 16 + r16];
     double w[SN];
 #pragma unroll
@@ -473,12 +351,8 @@ __global__ void __launch_bounds__(256) k_batch_pass2(BatchArgs a) {
   const int64_t row0 = a.seg_row0[seg];
   const int rows = a.seg_rows[seg];
   double* rec = a.rec2 + (int64_t)seg * BATCH_REC2;
-  switch (((int)P[BP_M] + 15) >> 4) {
-    case 1: pass2_body<1, ARD>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, red, el_s); break;
-    case 2: pass2_body<2, ARD>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, red, el_s); break;
-    case 3: pass2_body<3, ARD>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, red, el_s); break;
-    default: pass2_body<4, ARD>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, red, el_s); break;
-  }
+  SGP_BATCH_NT(P[BP_M],
+               pass2_body<NT, ARD>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, red, el_s))
 }
 
 // ------------------------------------------------------------------------------ finish
@@ -522,35 +396,16 @@ __global__ void __launch_bounds__(256) k_batch_post(BatchArgs a, double* __restr
   const double sig2 = P[BP_SIG2];
   // K22's diagonal: delta, and tau^2 + delta where the evaluation was a Laplace one (quirk Q1)
   const double delta = P[BP_OBJ] == 2.0 ? P[BP_TAU2] + P[BP_DELTA] : P[BP_DELTA];
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    A[i * MM + j] = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j)) + (i == j ? delta : 0.0);
+  for_mm(m, [&](int i, int j) {
+    A[i * MM + j] = k22(P, d, i, j, sig2, delta);
     Bm[i * MM + j] = post[i * MM + j];
-  }
+  });
   if (tid < m) u_s[tid] = post[MM * MM + tid];
   __syncthreads();
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    double s = 0.0;
-    for (int k = 0; k < m; ++k) s = fma(A[i * MM + k], Bm[k * MM + j], s);
-    T[i * MM + j] = s;
-  }
-  __syncthreads();
+  sandwich(A, Bm, T, m);
   double* r = res + (int64_t)prob * (MM * MM + MM);
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    double s = 0.0;
-    for (int k = 0; k < m; ++k) s = fma(T[i * MM + k], A[k * MM + j], s);
-    r[i * MM + j] = s;
-  }
-  if (tid < m) {
-    double s = 0.0;
-    for (int k = 0; k < m; ++k) s = fma(A[tid * MM + k], u_s[k], s);
-    r[MM * MM + tid] = s;
-  }
+  for_mm(m, [&](int i, int j) { r[i * MM + j] = dot_mm(T, A, i, j, m); });
+  if (tid < m) r[MM * MM + tid] = mat_vec_row(A, u_s, tid, m);
 }
 
 // ------------------------------------------------------------------------------ prediction
@@ -573,23 +428,14 @@ __global__ void __launch_bounds__(256) k_batch_pred_mm(BatchArgs a, BatchPredArg
   const double sig2 = P[BP_SIG2], tau2 = P[BP_TAU2], delta = P[BP_DELTA];
   // predict_laplace(family != "gaussian") keeps tau^2 on Sigma22's diagonal (sec. 0s)
   const double dg = P[BP_OBJ] == 2.0 ? tau2 + delta : delta;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    A[i * MM + j] = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j)) + (i == j ? dg : 0.0);
-  }
   double ld22 = 0.0;
-  const int st = sweep_spd(A, m, ck, &ld22);
+  const int st = k22_inverse(P, d, dg, A, ck, &ld22);
   double* w = p.pw + (int64_t)prob * BATCH_PW;
   // predict_laplace's constant has no delta (laplace_approx_prediction.R:3-123; sec. 0q)
   if (tid == 0)
     w[BPW_C0] = st ? NAN : (P[BP_OBJ] != 0.0 ? tau2 + sig2 : (tau2 + sig2) + delta);
   if (st) return;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    w[i * MM + j] = post[i * MM + j] - A[i * MM + j];
-  }
+  for_mm(m, [&](int i, int j) { w[i * MM + j] = post[i * MM + j] - A[i * MM + j]; });
 }
 
 // One test segment: 64 rows per step in pass 2's layout (lane l on row l & 15 and knots
@@ -614,25 +460,14 @@ __device__ __forceinline__ void predict_body(const BatchArgs& a, const BatchPred
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, g = lane >> 4;
   const bool score = p.score != 0;
 
-  for (int q = tid; q < d * Mp; q += 256) {
-    const int c = q / Mp, j = q - c * Mp;
-    xu_s[(c * 4 + (j & 3)) * SN + (j >> 2)] = P[BP_U + c * MM + j];
-  }
-  for (int q = tid; q < Mp * Mp; q += 256) {
-    const int i = q / Mp, j = q - i * Mp;
-    pp_s[q] = (i < m && j < m) ? w[i * MM + j] : 0.0;
-  }
-  for (int q = tid; q < Mp; q += 256) u_s[(q & 3) * SN + (q >> 2)] = q < m ? post[MM * MM + q] : 0.0;
-  for (int q = tid; q < d; q += 256) rl_s[q] = P[BP_RL + q];
+  stage_knots(P, d, Mp, SN, xu_s, rl_s);
+  stage_mat(w, m, Mp, pp_s);
+  stage_vec(post + MM * MM, m, Mp, SN, u_s);
 
   double ssum = 0.0;   // thread q < 4: stats term q over the rows so far
   for (int step = 0; step * 64 < rows; ++step) {
     __syncthreads();   // the staging above / the previous step's reads of xs and writes of sv
-    for (int q = tid; q < d * 64; q += 256) {
-      const int c = q >> 6, i = q & 63;
-      const int row = step * 64 + i;
-      xs[q] = row < rows ? p.Xt[(int64_t)c * p.ldxt + row0 + row] : 0.0;
-    }
+    stage_x(p.Xt, p.ldxt, row0, rows, step, d, xs);
     if (tid < 64) {
       const int row = step * 64 + tid;
       mus[tid] = row < rows ? p.mut[row0 + row] : 0.0;
@@ -643,47 +478,11 @@ __device__ __forceinline__ void predict_body(const BatchArgs& a, const BatchPred
     __syncthreads();
 
     const int row = step * 64 + wv * 16 + r16;
-    const bool iv = row < rows;
-    const double* xr = xs + wv * 16 + r16;
     double e2[SN], kf[SN];
-#pragma unroll
-    for (int s = 0; s < SN; ++s) e2[s] = 0.0;
-    for (int c = 0; c < d; ++c) {
-      const double xc = xr[c * 64], rl = rl_s[c];
-      const double* u = xu_s + (c * 4 + g) * SN;
-#pragma unroll
-      for (int s = 0; s < SN; ++s) {
-        const double t = (xc - u[s]) * rl;   // the raw difference first: coincidence stays exact
-        e2[s] = fma(t, t, e2[s]);
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < SN; ++s) {
-      const double v = sig2 * sgp_exp_nonpos(-0.5 * e2[s]);
-      kf[s] = (iv && 4 * s + g < m) ? v : 0.0;
-    }
+    const bool iv = rows_k<SN>(xs, xu_s, rl_s, d, m, sig2, rows, step, e2, kf);
     d4 acc[NT];
-#pragma unroll
-    for (int cb = 0; cb < NT; ++cb) acc[cb] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < SN; ++s)
-#pragma unroll
-      for (int cb = 0; cb < NT; ++cb)
-        acc[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(pp_s[(4 * s + g) * Mp + 16 * cb + r16],
-                                                       kf[s], acc[cb], 0, 0, 0);
-    double ku = 0.0, kq = 0.0;
-#pragma unroll
-    for (int cb = 0; cb < NT; ++cb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int s = 4 * cb + r;
-        ku = fma(kf[s], u_s[g * SN + s], ku);
-        kq = fma(acc[cb][r], kf[s], kq);
-      }
-    ku += __shfl_xor(ku, 16, 64);
-    ku += __shfl_xor(ku, 32, 64);
-    kq += __shfl_xor(kq, 16, 64);
-    kq += __shfl_xor(kq, 32, 64);
+    kmat<NT>(pp_s, kf, acc);
+    const double ku = k_dot<SN>(kf, u_s, g), kq = row_dot<NT>(acc, kf);
     if (g == 0) {
       const int i = wv * 16 + r16;
       const double mean = mus[i] + ku, var = c0 + kq;
@@ -726,12 +525,8 @@ __global__ void __launch_bounds__(256) k_batch_predict(BatchArgs a, BatchPredArg
   const int64_t row0 = p.seg_row0[seg], out0 = p.seg_out[seg];
   const int rows = p.seg_rows[seg];
   double* rec = p.rec + (int64_t)seg * BATCH_PREC;
-  switch (((int)post[MM * MM + MM + BP_M] + 15) >> 4) {
-    case 1: predict_body<1>(a, p, post, w, row0, rows, out0, rec, xu_s, pp_s, vec_s, xs, sv); break;
-    case 2: predict_body<2>(a, p, post, w, row0, rows, out0, rec, xu_s, pp_s, vec_s, xs, sv); break;
-    case 3: predict_body<3>(a, p, post, w, row0, rows, out0, rec, xu_s, pp_s, vec_s, xs, sv); break;
-    default: predict_body<4>(a, p, post, w, row0, rows, out0, rec, xu_s, pp_s, vec_s, xs, sv); break;
-  }
+  SGP_BATCH_NT(post[MM * MM + MM + BP_M],
+               predict_body<NT>(a, p, post, w, row0, rows, out0, rec, xu_s, pp_s, vec_s, xs, sv))
 }
 
 // the segments' records, in segment order
@@ -773,16 +568,9 @@ __device__ __forceinline__ void knot_body(const BatchArgs& a, const double* __re
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, g = lane >> 4;
   double* wt = wt_s + wv * 16 * KXS;   // the wave's own W tile [row][knot]
 
-  for (int q = tid; q < d * Mp; q += 256) {
-    const int c = q / Mp, j = q - c * Mp;
-    xu_s[(c * 4 + (j & 3)) * SN + (j >> 2)] = P[BP_U + c * MM + j];
-  }
-  for (int q = tid; q < Mp * Mp; q += 256) {
-    const int i = q / Mp, j = q - i * Mp;
-    pp_s[q] = (i < m && j < m) ? pm[i * MM + j] : 0.0;
-  }
-  for (int q = tid; q < Mp; q += 256) u_s[(q & 3) * SN + (q >> 2)] = q < m ? pm[BPM_U + q] : 0.0;
-  for (int q = tid; q < d; q += 256) rl_s[q] = P[BP_RL + q];
+  stage_knots(P, d, Mp, SN, xu_s, rl_s);
+  stage_mat(pm, m, Mp, pp_s);
+  stage_vec(pm + BPM_U, m, Mp, SN, u_s);
   double ob[NCB];   // the offset of this lane's coordinate in block cb
   bool cv[NCB];
 #pragma unroll
@@ -802,45 +590,17 @@ __device__ __forceinline__ void knot_body(const BatchArgs& a, const double* __re
 
   for (int step = 0; step * 64 < rows; ++step) {
     __syncthreads();   // the staging above / the previous step's reads of xs, rs and wt
-    for (int q = tid; q < d * 64; q += 256) {
-      const int c = q >> 6, i = q & 63;
-      const int row = step * 64 + i;
-      xs[c * KXS + i] = row < rows ? a.X[(int64_t)c * a.ldx + row0 + row] : 0.0;
-    }
+    stage_x(a.X, a.ldx, row0, rows, step, d, xs, KXS);
     if (tid < 64) {
       const int row = step * 64 + tid;
       rs[tid] = row < rows ? (a.y[row0 + row] - a.mu[row0 + row]) * rz : 0.0;
     }
     __syncthreads();
 
-    const bool iv = step * 64 + wv * 16 + r16 < rows;
-    const double* xr = xs + wv * 16 + r16;
     double e2[SN], kf[SN];
-#pragma unroll
-    for (int s = 0; s < SN; ++s) e2[s] = 0.0;
-    for (int c = 0; c < d; ++c) {
-      const double xc = xr[c * KXS], rl = rl_s[c];
-      const double* u = xu_s + (c * 4 + g) * SN;
-#pragma unroll
-      for (int s = 0; s < SN; ++s) {
-        const double t = (xc - u[s]) * rl;   // the raw difference first, as in pass 2
-        e2[s] = fma(t, t, e2[s]);
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < SN; ++s) {
-      const double v = sig2 * sgp_exp_nonpos(-0.5 * e2[s]);
-      kf[s] = (iv && 4 * s + g < m) ? v : 0.0;
-    }
+    rows_k<SN>(xs, xu_s, rl_s, d, m, sig2, rows, step, e2, kf, KXS);
     d4 acc[NT];
-#pragma unroll
-    for (int cb = 0; cb < NT; ++cb) acc[cb] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < SN; ++s)
-#pragma unroll
-      for (int cb = 0; cb < NT; ++cb)
-        acc[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(pp_s[(4 * s + g) * Mp + 16 * cb + r16],
-                                                       kf[s], acc[cb], 0, 0, 0);
+    kmat<NT>(pp_s, kf, acc);
     const double ri = rs[wv * 16 + r16];
 #pragma unroll
     for (int cb = 0; cb < NT; ++cb)
@@ -903,7 +663,7 @@ __device__ __forceinline__ void knot_body(const BatchArgs& a, const double* __re
     const int k = q / d, c = q - k * d;
     rec[k * SGP_MAXD + c] = tb[k * SGP_MAXD + c];
   }
-  if (tid < m) rec[BK_CS + tid] = ((cw[tid] + cw[MM + tid]) + cw[2 * MM + tid]) + cw[3 * MM + tid];
+  if (tid < m) rec[BK_CS + tid] = wave_sum4(cw, tid);
 }
 
 __global__ void __launch_bounds__(256) k_batch_knot_pass(BatchArgs a) {
@@ -918,17 +678,10 @@ __global__ void __launch_bounds__(256) k_batch_knot_pass(BatchArgs a) {
   const int64_t row0 = a.seg_row0[seg];
   const int rows = a.seg_rows[seg];
   double* rec = a.rec3 + (int64_t)seg * BATCH_REC3;
-#define SGP_KNOT_CASE(NT)                                                             \
-  if (a.d > 16) knot_body<NT, 2>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, wt_s); \
-  else knot_body<NT, 1>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, wt_s);          \
-  break;
-  switch (((int)P[BP_M] + 15) >> 4) {
-    case 1: SGP_KNOT_CASE(1)
-    case 2: SGP_KNOT_CASE(2)
-    case 3: SGP_KNOT_CASE(3)
-    default: SGP_KNOT_CASE(4)
-  }
-#undef SGP_KNOT_CASE
+  SGP_BATCH_NT(
+      P[BP_M],
+      if (a.d > 16) knot_body<NT, 2>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, wt_s);
+      else knot_body<NT, 1>(a, P, pm, row0, rows, rec, xu_s, pp_s, vec_s, xs, wt_s))
 }
 
 // The segments' records in segment order, the K22 part from H and the knots, 1 / l_c^2 and the
@@ -944,8 +697,7 @@ __global__ void __launch_bounds__(256) k_batch_knot_finish(BatchArgs a) {
   const int seg0 = (int)P[BP_SEG0], nseg = (int)P[BP_NSEG];
   const double* rec = a.rec3 + (int64_t)seg0 * BATCH_REC3;
   const double* hk = a.hk + (int64_t)prob * BR_T;
-  for (int e = tid; e < m * MM; e += 256)
-    if ((e & (MM - 1)) < m) H[e] = hk[e];
+  for_mm(m, [&](int i, int j) { H[i * MM + j] = hk[i * MM + j]; });
   if (tid < m) cs[tid] = rec_sum(rec + BK_CS + tid, BATCH_REC3, nseg);
   __syncthreads();
   double* gk = a.gk + (int64_t)P[BP_GOFF];

@@ -14,14 +14,15 @@
 //                                                                k_bf_pass2, per segment
 //   G22 = -1/2 u u^T + 1/2 (A - Bm^-1) + 1/2 A S_omega A, H = G22 o Kuu, the gradient
 //                                                                k_bf_g22, per problem, in LDS
-// The segments, the 64-row steps and the per-row bounds test are k_batch.hip's.  Both row passes
-// form k in k_fit_scan's operand layout of v_mfma_f64_16x16x4_f64 (lane l on row l & 15 and knots
-// 4 s + (l >> 4)), in which K A and K Bm^-1 are MFMAs against an operand in LDS and q, p and
-// k^T u are fma chains in the lane and one xor-shuffle over the four lane groups.  Each wave
-// then turns its 16 x Mp tile of k through wave-private LDS into pass 1's layout (knot on l & 15,
-// rows 4 q + (l >> 4)) for the nb (nb + 1) / 2 block pairs of the rank-update: both operands
-// scaled by sqrt(w_i) for S, one operand scaled by omega_i for S_omega, whose weights take both
-// signs.  The row weights are recomputed from k in each pass, so nothing is indexed by the
+// The segments, the 64-row steps and the per-row bounds test are the VI batch's (k_batch.hip).
+// Both row passes are built from sgp_batch_dev.h's pieces: k in k_fit_scan's operand layout of
+// v_mfma_f64_16x16x4_f64 (rows_k), in which K A and K Bm^-1 are MFMAs against an operand in LDS
+// (kmat) and q, p and k^T u are fma chains in the lane and one xor-shuffle over the four lane
+// groups (row_dot, k_dot); the wave's 16 x Mp tile of k turned through wave-private LDS for the
+// nb (nb + 1) / 2 block pairs of the rank update: both operands scaled by sqrt(w_i) for S
+// (rank_update_root), one operand scaled by omega_i for S_omega, whose weights take both signs
+// (rank_update_signed); the tails (pass1_tail, grad_terms, grad_tail).  This file keeps the row
+// terms and G.  The row weights are recomputed from k in each pass, so nothing is indexed by the
 // resident row and aliased row ranges need no work vector.  Every sum has a fixed order, no
 // kernel uses atomics, and nothing a problem computes reads another problem's data.
 #include <math.h>
@@ -31,8 +32,6 @@
 
 namespace {
 
-constexpr int FXS = 68;   // the wave-private k tile's row stride (doubles)
-
 // ------------------------------------------------------------------------------ K22's stage
 __global__ void __launch_bounds__(256) k_bf_k22(BatchArgs a) {
   __shared__ __attribute__((aligned(16))) double A[MM * MM];
@@ -40,17 +39,11 @@ __global__ void __launch_bounds__(256) k_bf_k22(BatchArgs a) {
   const int prob = blockIdx.x, tid = threadIdx.x;
   const double* P = a.par + (int64_t)prob * a.pst;
   if (P[BP_ACTIVE] == 0.0) return;
-  const int d = a.d, m = (int)P[BP_M];
-  const double sig2 = P[BP_SIG2], delta = P[BP_DELTA];
+  const int m = (int)P[BP_M];
   double* out = a.out + (int64_t)prob * BATCH_OUT;
   double* fw = a.fw + (int64_t)prob * BATCH_FW;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    A[i * MM + j] = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j)) + (i == j ? delta : 0.0);
-  }
   double ld22 = 0.0;
-  const int st = sweep_spd(A, m, ck, &ld22);
+  const int st = k22_inverse(P, a.d, P[BP_DELTA], A, ck, &ld22);
   if (tid == 0) {
     out[0] = st ? NAN : 0.0;
     out[1] = (double)st;
@@ -58,72 +51,16 @@ __global__ void __launch_bounds__(256) k_bf_k22(BatchArgs a) {
     fw[BF_BAD] = 0.0;
   }
   if (st) return;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    fw[BF_A + i * MM + j] = A[i * MM + j];
-  }
+  for_mm(m, [&](int i, int j) { fw[BF_A + i * MM + j] = A[i * MM + j]; });
 }
 
-// k of the step's rows in k_fit_scan's layout: e2[s] the scaled squared distance of row r16 of
-// the wave's 16 and knot 4 s + g, kf[s] the covariance (zero beyond the rows and the knots)
-#define SGP_BF_ROWS_K()                                                            \
-  const bool iv = step * 64 + wv * 16 + r16 < rows;                                \
-  const double* xr = xs + wv * 16 + r16;                                           \
-  double e2[SN], kf[SN];                                                           \
-  _Pragma("unroll") for (int s = 0; s < SN; ++s) e2[s] = 0.0;                      \
-  for (int c = 0; c < d; ++c) {                                                    \
-    const double xc = xr[c * 64], rl = rl_s[c];                                    \
-    const double* u = xu_s + (c * 4 + g) * SN;                                     \
-    _Pragma("unroll") for (int s = 0; s < SN; ++s) {                               \
-      const double t = (xc - u[s]) * rl; /* the raw difference first, as in pass 2 */ \
-      e2[s] = fma(t, t, e2[s]);                                                    \
-    }                                                                              \
-  }                                                                                \
-  _Pragma("unroll") for (int s = 0; s < SN; ++s) {                                 \
-    const double v = sig2 * sgp_exp_nonpos(-0.5 * e2[s]);                          \
-    kf[s] = (iv && 4 * s + g < m) ? v : 0.0;                                       \
-  }
-
-// sum over the lane's knots of acc o k, then over the four lane groups: every lane of a row
-// ends with the same bits
-template <int NT>
-__device__ __forceinline__ double row_dot(const d4* acc, const double* kf) {
-  double v = 0.0;
-#pragma unroll
-  for (int cb = 0; cb < NT; ++cb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v = fma(acc[cb][r], kf[4 * cb + r], v);
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-
-// the four waves' partial block pairs, added in wave order into lds (row stride 64), mirrored
-// into rec (row stride 64)
-template <int NT>
-__device__ __forceinline__ void store_pairs(const d4* acc, double* lds, double* __restrict__ rec) {
-  constexpr int Mp = 16 * NT;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, g = lane >> 4;
-  for (int w = 0; w < 4; ++w) {
-    __syncthreads();
-    if (wv == w) {
-      int p = 0;
-#pragma unroll
-      for (int bi = 0; bi < NT; ++bi)
-#pragma unroll
-        for (int bj = bi; bj < NT; ++bj, ++p)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            double* s = lds + (16 * bi + 4 * r + g) * MM + 16 * bj + r16;
-            *s = w ? *s + acc[p][r] : acc[p][r];
-          }
-    }
-  }
-  __syncthreads();
-  for (int q = tid; q < Mp * Mp; q += 256) {
-    const int i = q / Mp, j = q - i * Mp;
-    rec[i * MM + j] = (i >> 4) > (j >> 4) ? lds[j * MM + i] : lds[i * MM + j];
+// the step's r = y - mu, zero beyond the segment
+__device__ __forceinline__ void stage_r(const BatchArgs& a, int64_t row0, int rows, int step,
+                                        double* rs) {
+  const int tid = threadIdx.x;
+  if (tid < 64) {
+    const int row = step * 64 + tid;
+    rs[tid] = row < rows ? a.y[row0 + row] - a.mu[row0 + row] : 0.0;
   }
 }
 
@@ -145,15 +82,8 @@ __device__ __forceinline__ void bf_pass1_body(const BatchArgs& a, const double* 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, g = lane >> 4;
   double* wt = wt_s + wv * 16 * FXS;   // the wave's own k tile [row][knot]
 
-  for (int q = tid; q < d * Mp; q += 256) {
-    const int c = q / Mp, j = q - c * Mp;
-    xu_s[(c * 4 + (j & 3)) * SN + (j >> 2)] = P[BP_U + c * MM + j];
-  }
-  for (int q = tid; q < Mp * Mp; q += 256) {
-    const int i = q / Mp, j = q - i * Mp;
-    pa_s[q] = (i < m && j < m) ? fw[BF_A + i * MM + j] : 0.0;
-  }
-  for (int q = tid; q < d; q += 256) rl_s[q] = P[BP_RL + q];
+  stage_knots(P, d, Mp, SN, xu_s, rl_s);
+  stage_mat(fw + BF_A, m, Mp, pa_s);
 
   d4 acc[NT * (NT + 1) / 2];
 #pragma unroll
@@ -165,27 +95,14 @@ __device__ __forceinline__ void bf_pass1_body(const BatchArgs& a, const double* 
 
   for (int step = 0; step * 64 < rows; ++step) {
     __syncthreads();   // the staging above / the previous step's reads of xs, the vectors and wt
-    for (int q = tid; q < d * 64; q += 256) {
-      const int c = q >> 6, i = q & 63;
-      const int row = step * 64 + i;
-      xs[q] = row < rows ? a.X[(int64_t)c * a.ldx + row0 + row] : 0.0;
-    }
-    if (tid < 64) {
-      const int row = step * 64 + tid;
-      rs[tid] = row < rows ? a.y[row0 + row] - a.mu[row0 + row] : 0.0;
-    }
+    stage_x(a.X, a.ldx, row0, rows, step, d, xs);
+    stage_r(a, row0, rows, step, rs);
     __syncthreads();
 
-    SGP_BF_ROWS_K()
+    double e2[SN], kf[SN];
+    const bool iv = rows_k<SN>(xs, xu_s, rl_s, d, m, sig2, rows, step, e2, kf);
     d4 qa[NT];
-#pragma unroll
-    for (int cb = 0; cb < NT; ++cb) qa[cb] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < SN; ++s)
-#pragma unroll
-      for (int cb = 0; cb < NT; ++cb)
-        qa[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa_s[(4 * s + g) * Mp + 16 * cb + r16],
-                                                      kf[s], qa[cb], 0, 0, 0);
+    kmat<NT>(pa_s, kf, qa);
     const double z = c0 - row_dot<NT>(qa, kf);
     const double w = 1.0 / z;
     if (g == 0) {
@@ -199,50 +116,13 @@ __device__ __forceinline__ void bf_pass1_body(const BatchArgs& a, const double* 
       sw_s[i] = iv ? sqrt(w) : 0.0;
       wr_s[i] = iv ? w * ri : 0.0;
     }
-#pragma unroll
-    for (int s = 0; s < SN; ++s) wt[r16 * FXS + 4 * s + g] = kf[s];
+    put_ktile<SN>(wt, kf);
     __syncthreads();   // the k tile and the weights are read across the wave's lanes
-    // S[16 bi + i][16 bj + j] += sum over the wave's 16 rows: A[i][row] = B[row][j] = sqrt(w) k
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = 4 * q + g;
-      const double sq = sw_s[wv * 16 + i], wr = wr_s[wv * 16 + i];
-      double kw[NT];
-#pragma unroll
-      for (int b = 0; b < NT; ++b) {
-        const double k1 = wt[i * FXS + 16 * b + r16];
-        tacc[b] = fma(k1, wr, tacc[b]);
-        kw[b] = k1 * sq;
-      }
-      int p = 0;
-#pragma unroll
-      for (int bi = 0; bi < NT; ++bi)
-#pragma unroll
-        for (int bj = bi; bj < NT; ++bj, ++p)
-          acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(kw[bi], kw[bj], acc[p], 0, 0, 0);
-    }
+    rank_update_root<NT, true>(wt, sw_s, wr_s, acc, tacc);
   }
 
   store_pairs<NT>(acc, pa_s, rec);   // over A, which is dead
-#pragma unroll
-  for (int b = 0; b < NT; ++b) {
-    double t = tacc[b];
-    t += __shfl_xor(t, 16, 64);
-    t += __shfl_xor(t, 32, 64);
-    if (g == 0) tw[wv * MM + 16 * b + r16] = t;
-  }
-  if (g == 0) {
-    red[wv * 16 + r16] = swrr;
-    red[MM + wv * 16 + r16] = slz;
-    red[2 * MM + wv * 16 + r16] = bad;
-  }
-  __syncthreads();
-  if (tid < Mp) rec[BR_T + tid] = ((tw[tid] + tw[MM + tid]) + tw[2 * MM + tid]) + tw[3 * MM + tid];
-  if (tid < 3) {
-    double v = 0.0;
-    for (int q = 0; q < 64; ++q) v += red[tid * MM + q];
-    rec[BR_RR + tid] = v;
-  }
+  pass1_tail<NT>(tacc, swrr, slz, bad, tw, red, rec);
 }
 
 __global__ void __launch_bounds__(256) k_bf_pass1(BatchArgs a) {
@@ -257,12 +137,8 @@ __global__ void __launch_bounds__(256) k_bf_pass1(BatchArgs a) {
   const int64_t row0 = a.seg_row0[seg];
   const int rows = a.seg_rows[seg];
   double* rec = a.rec1 + (int64_t)seg * BATCH_REC1;
-  switch (((int)P[BP_M] + 15) >> 4) {
-    case 1: bf_pass1_body<1>(a, P, fw, row0, rows, rec, xu_s, pa_s, vec_s, xs, wt_s, tw); break;
-    case 2: bf_pass1_body<2>(a, P, fw, row0, rows, rec, xu_s, pa_s, vec_s, xs, wt_s, tw); break;
-    case 3: bf_pass1_body<3>(a, P, fw, row0, rows, rec, xu_s, pa_s, vec_s, xs, wt_s, tw); break;
-    default: bf_pass1_body<4>(a, P, fw, row0, rows, rec, xu_s, pa_s, vec_s, xs, wt_s, tw); break;
-  }
+  SGP_BATCH_NT(P[BP_M],
+               bf_pass1_body<NT>(a, P, fw, row0, rows, rec, xu_s, pa_s, vec_s, xs, wt_s, tw))
 }
 
 // ------------------------------------------------------------------------------ Bm's stage
@@ -292,13 +168,10 @@ __global__ void __launch_bounds__(256) k_bf_mm(BatchArgs a) {
     }
     return;
   }
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
+  for_mm(m, [&](int i, int j) {
     const double s = rec_sum(rec + i * MM + j, BATCH_REC1, nseg);
-    const double kuu = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j));
-    Bm[i * MM + j] = (kuu + (i == j ? delta : 0.0)) + s;
-  }
+    Bm[i * MM + j] = k22(P, d, i, j, sig2, delta) + s;
+  });
   if (tid < m) t_s[tid] = rec_sum(rec + BR_T + tid, BATCH_REC1, nseg);
 
   double ldB = 0.0;
@@ -310,11 +183,7 @@ __global__ void __launch_bounds__(256) k_bf_mm(BatchArgs a) {
     }
     return;
   }
-  if (tid < m) {
-    double s = 0.0;
-    for (int k = 0; k < m; ++k) s = fma(Bm[tid * MM + k], t_s[k], s);
-    u_s[tid] = s;
-  }
+  if (tid < m) u_s[tid] = mat_vec_row(Bm, t_s, tid, m);
   __syncthreads();
   const double tu = block_sum(tid < m ? t_s[tid] * u_s[tid] : 0.0, red);
 
@@ -324,27 +193,13 @@ __global__ void __launch_bounds__(256) k_bf_mm(BatchArgs a) {
   const double quad = -0.5 * wrr + 0.5 * tu;
   const double det_part = -0.5 * (slz - logdet22 + ldB);
   if (tid == 0) out[0] = quad + det_part - (n / 2.0) * log(2.0 * M_PI);
-  // what sgp_batch_posterior_u and sgp_batch_predict need, where the VI evaluation leaves it
-  double* post = a.post + (int64_t)prob * a.post_stride;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    post[i * MM + j] = Bm[i * MM + j];
-  }
-  if (tid < m) post[MM * MM + tid] = u_s[tid];
-  for (int q = tid; q < a.pst; q += 256) post[MM * MM + MM + q] = P[q];
+  store_post(a, prob, P, Bm, u_s, m);   // where the VI evaluation leaves it
   if (a.obj_only) return;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    fw[BF_B + i * MM + j] = Bm[i * MM + j];
-  }
+  for_mm(m, [&](int i, int j) { fw[BF_B + i * MM + j] = Bm[i * MM + j]; });
   if (tid < m) fw[BF_U + tid] = u_s[tid];
 }
 
 // ------------------------------------------------------------------------------ row pass 2
-// el_s (ARD): [c][wave][16] slots, one per row lane of a wave: the lane groups are folded by
-// shuffles first, so the d running sums take 16 KiB beside the two m x m operands
 template <int NT, bool ARD>
 __device__ __forceinline__ void bf_pass2_body(const BatchArgs& a, const double* __restrict__ P,
                                               const double* __restrict__ fw, int64_t row0, int rows,
@@ -362,18 +217,10 @@ __device__ __forceinline__ void bf_pass2_body(const BatchArgs& a, const double* 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, g = lane >> 4;
   double* wt = wt_s + wv * 16 * FXS;   // the wave's own k tile [row][knot]
 
-  for (int q = tid; q < d * Mp; q += 256) {
-    const int c = q / Mp, j = q - c * Mp;
-    xu_s[(c * 4 + (j & 3)) * SN + (j >> 2)] = P[BP_U + c * MM + j];
-  }
-  for (int q = tid; q < Mp * Mp; q += 256) {
-    const int i = q / Mp, j = q - i * Mp;
-    const bool in = i < m && j < m;
-    pa_s[q] = in ? fw[BF_A + i * MM + j] : 0.0;
-    pb_s[q] = in ? fw[BF_B + i * MM + j] : 0.0;
-  }
-  for (int q = tid; q < Mp; q += 256) u_s[(q & 3) * SN + (q >> 2)] = q < m ? fw[BF_U + q] : 0.0;
-  for (int q = tid; q < d; q += 256) rl_s[q] = P[BP_RL + q];
+  stage_knots(P, d, Mp, SN, xu_s, rl_s);
+  stage_mat(fw + BF_A, m, Mp, pa_s);
+  stage_mat(fw + BF_B, m, Mp, pb_s);
+  stage_vec(fw + BF_U, m, Mp, SN, u_s);
   if (ARD)
     for (int q = tid; q < d * 64; q += 256) el_s[q] = 0.0;
 
@@ -384,35 +231,15 @@ __device__ __forceinline__ void bf_pass2_body(const BatchArgs& a, const double* 
 
   for (int step = 0; step * 64 < rows; ++step) {
     __syncthreads();   // the staging above / the previous step's reads of xs, the vectors and wt
-    for (int q = tid; q < d * 64; q += 256) {
-      const int c = q >> 6, i = q & 63;
-      const int row = step * 64 + i;
-      xs[q] = row < rows ? a.X[(int64_t)c * a.ldx + row0 + row] : 0.0;
-    }
-    if (tid < 64) {
-      const int row = step * 64 + tid;
-      rs[tid] = row < rows ? a.y[row0 + row] - a.mu[row0 + row] : 0.0;
-    }
+    stage_x(a.X, a.ldx, row0, rows, step, d, xs);
+    stage_r(a, row0, rows, step, rs);
     __syncthreads();
 
-    SGP_BF_ROWS_K()
+    double e2[SN], kf[SN];
+    const bool iv = rows_k<SN>(xs, xu_s, rl_s, d, m, sig2, rows, step, e2, kf);
     d4 qa[NT], qb[NT];
-#pragma unroll
-    for (int cb = 0; cb < NT; ++cb) qa[cb] = qb[cb] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < SN; ++s)
-#pragma unroll
-      for (int cb = 0; cb < NT; ++cb) {
-        qa[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa_s[(4 * s + g) * Mp + 16 * cb + r16],
-                                                      kf[s], qa[cb], 0, 0, 0);
-        qb[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(pb_s[(4 * s + g) * Mp + 16 * cb + r16],
-                                                      kf[s], qb[cb], 0, 0, 0);
-      }
-    double ku = 0.0;
-#pragma unroll
-    for (int s = 0; s < SN; ++s) ku = fma(kf[s], u_s[g * SN + s], ku);
-    ku += __shfl_xor(ku, 16, 64);
-    ku += __shfl_xor(ku, 32, 64);
+    kmat2<NT>(pa_s, pb_s, kf, qa, qb);
+    const double ku = k_dot<SN>(kf, u_s, g);
     const double z = c0 - row_dot<NT>(qa, kf);   // pass 1's bits
     const double pi = row_dot<NT>(qb, kf);
     const double wi = iv ? 1.0 / z : 0.0;
@@ -422,79 +249,19 @@ __device__ __forceinline__ void bf_pass2_body(const BatchArgs& a, const double* 
       som += om;
       om_s[wv * 16 + r16] = om;
     }
-    double w[SN];
-#pragma unroll
-    for (int cb = 0; cb < NT; ++cb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int s = 4 * cb + r;
-        // G = alpha u^T - w K Bm^-1 - omega K A
-        const double gv = fma(al, u_s[g * SN + s], -fma(wi, qb[cb][r], om * qa[cb][r]));
-        w[s] = gv * kf[s];
-        esig += w[s];
-        if (!ARD) el = fma(w[s], e2[s], el);
-        // quirk Q5: the tau derivative of a pair whose raw differences are all zero
-        if (e2[s] == 0.0 && iv && 4 * s + g < m) csum += gv;
-      }
-    if (ARD)
-      for (int c = 0; c < d; ++c) {
-        const double xc = xr[c * 64], rl = rl_s[c];
-        const double* u = xu_s + (c * 4 + g) * SN;
-        double v = 0.0;
-#pragma unroll
-        for (int s = 0; s < SN; ++s) {
-          const double t = (xc - u[s]) * rl;
-          v = fma(w[s], t * t, v);
-        }
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
-        if (g == 0) el_s[(c * 4 + wv) * 16 + r16] += v;   // the lane's own slot
-      }
-#pragma unroll
-    for (int s = 0; s < SN; ++s) wt[r16 * FXS + 4 * s + g] = kf[s];
+    // G = alpha u^T - w K Bm^-1 - omega K A
+    grad_terms<NT, ARD>(
+        [&](int cb, int r, int s) {
+          return fma(al, u_s[g * SN + s], -fma(wi, qb[cb][r], om * qa[cb][r]));
+        },
+        kf, e2, iv, m, d, xs, xu_s, rl_s, el_s, esig, el, csum);
+    put_ktile<SN>(wt, kf);
     __syncthreads();   // the k tile and omega are read across the wave's lanes
-    // S_omega[16 bi + i][16 bj + j] += sum over the wave's 16 rows: A[i][row] = omega k,
-    // B[row][j] = k: omega takes both signs, so only one operand carries it
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = 4 * q + g;
-      const double oi = om_s[wv * 16 + i];
-      double k1[NT], ko[NT];
-#pragma unroll
-      for (int b = 0; b < NT; ++b) {
-        k1[b] = wt[i * FXS + 16 * b + r16];
-        ko[b] = k1[b] * oi;
-      }
-      int p = 0;
-#pragma unroll
-      for (int bi = 0; bi < NT; ++bi)
-#pragma unroll
-        for (int bj = bi; bj < NT; ++bj, ++p)
-          acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(ko[bi], k1[bj], acc[p], 0, 0, 0);
-    }
+    rank_update_signed<NT>(wt, om_s, acc);   // S_omega
   }
 
   store_pairs<NT>(acc, pa_s, rec);   // over A, which is dead
-  const double e0 = block_sum(esig, red);
-  const double e1 = block_sum(csum, red);
-  const double e2s = block_sum(som, red);
-  const int L = ARD ? d : 1;
-  if (ARD) {
-    __syncthreads();
-    if (tid < d) {
-      double v = 0.0;
-      for (int q = 0; q < 64; ++q) v += el_s[tid * 64 + q];   // wave, then row lane
-      rec[BQ_W + 1 + tid] = v;
-    }
-  } else {
-    const double e3 = block_sum(el, red);
-    if (tid == 0) rec[BQ_W + 1] = e3;
-  }
-  if (tid == 0) {
-    rec[BQ_W] = e0;
-    rec[BQ_W + 1 + L] = e1;
-    rec[BQ_W + 2 + L] = e2s;
-  }
+  grad_tail<ARD>(esig, el, csum, som, d, red, el_s, rec);
 }
 
 template <bool ARD>
@@ -512,22 +279,14 @@ __global__ void __launch_bounds__(256) k_bf_pass2(BatchArgs a) {
   const int64_t row0 = a.seg_row0[seg];
   const int rows = a.seg_rows[seg];
   double* rec = a.rec4 + (int64_t)seg * BATCH_REC4;
-#define SGP_BF_CASE(NT) \
-  bf_pass2_body<NT, ARD>(a, P, fw, row0, rows, rec, xu_s, pa_s, pb_s, vec_s, xs, wt_s, red, el_s); \
-  break;
-  switch (((int)P[BP_M] + 15) >> 4) {
-    case 1: SGP_BF_CASE(1)
-    case 2: SGP_BF_CASE(2)
-    case 3: SGP_BF_CASE(3)
-    default: SGP_BF_CASE(4)
-  }
-#undef SGP_BF_CASE
+  SGP_BATCH_NT(P[BP_M], bf_pass2_body<NT, ARD>(a, P, fw, row0, rows, rec, xu_s, pa_s, pb_s, vec_s,
+                                               xs, wt_s, red, el_s))
 }
 
 // ------------------------------------------------------------------------------ G22 and finish
 // G22 = -1/2 u u^T + 1/2 (K22^-1 - Bm^-1) + 1/2 K22^-1 S_omega K22^-1, contracted with
-// dK22 / dlog theta (sigma: 2 Kuu; l: Kuu |D|^2 / l^2; l_c: Kuu (D_c / l_c)^2; tau: none,
-// laplace_approx_gradient.R:899-902), then dlogp_dcov_par's gradient from the segments' sums
+// dK22 / dlog theta (contract_h; tau: none, laplace_approx_gradient.R:899-902), then
+// dlogp_dcov_par's gradient from the segments' sums
 __global__ void __launch_bounds__(256) k_bf_g22(BatchArgs a) {
   __shared__ __attribute__((aligned(16))) double A[MM * MM], Bi[MM * MM], S[MM * MM], T[MM * MM];
   __shared__ double u_s[MM], red[256], r2[SGP_MAXD + 4], g22[SGP_MAXD + 1];
@@ -546,61 +305,22 @@ __global__ void __launch_bounds__(256) k_bf_g22(BatchArgs a) {
   const double sig2 = P[BP_SIG2], tau2 = P[BP_TAU2];
   const int seg0 = (int)P[BP_SEG0], nseg = (int)P[BP_NSEG];
   const double* rec = a.rec4 + (int64_t)seg0 * BATCH_REC4;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
+  for_mm(m, [&](int i, int j) {
     A[i * MM + j] = fw[BF_A + i * MM + j];
     Bi[i * MM + j] = fw[BF_B + i * MM + j];
     S[i * MM + j] = rec_sum(rec + i * MM + j, BATCH_REC4, nseg);
-  }
+  });
   if (tid < m) u_s[tid] = fw[BF_U + tid];
   if (tid < L + 3) r2[tid] = rec_sum(rec + BQ_W + tid, BATCH_REC4, nseg);
   __syncthreads();
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    double s = 0.0;
-    for (int k = 0; k < m; ++k) s = fma(A[i * MM + k], S[k * MM + j], s);
-    T[i * MM + j] = s;
-  }
-  __syncthreads();
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    double s = 0.0;
-    for (int k = 0; k < m; ++k) s = fma(T[i * MM + k], A[k * MM + j], s);
+  sandwich(A, S, T, m);
+  for_mm(m, [&](int i, int j) {
+    const double s = dot_mm(T, A, i, j, m);
     const double gv = -0.5 * u_s[i] * u_s[j] + 0.5 * (A[i * MM + j] - Bi[i * MM + j]) + 0.5 * s;
-    const double kuu = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j));
-    S[i * MM + j] = gv * kuu;   // H: S is dead once T stands
-  }
+    S[i * MM + j] = gv * kuu(P, d, i, j, sig2);   // H: S is dead once T stands
+  });
   __syncthreads();
-  double h = 0.0;
-  for (int e = tid; e < m * MM; e += 256)
-    if ((e & (MM - 1)) < m) h += S[e];
-  const double hs = block_sum(h, red);
-  if (tid == 0) g22[0] = 2.0 * hs;
-  if (a.ard) {
-    for (int c = 0; c < d; ++c) {
-      double v = 0.0;
-      for (int e = tid; e < m * MM; e += 256) {
-        const int i = e >> 6, j = e & (MM - 1);
-        if (j >= m) continue;
-        const double t = (P[BP_U + c * MM + i] - P[BP_U + c * MM + j]) * P[BP_RL + c];
-        v = fma(S[i * MM + j], t * t, v);
-      }
-      const double vs = block_sum(v, red);
-      if (tid == 0) g22[1 + c] = vs;
-    }
-  } else {
-    double v = 0.0;
-    for (int e = tid; e < m * MM; e += 256) {
-      const int i = e >> 6, j = e & (MM - 1);
-      if (j >= m) continue;
-      v = fma(S[i * MM + j], knot_dist2(P, d, i, j), v);
-    }
-    const double vs = block_sum(v, red);
-    if (tid == 0) g22[1] = vs;
-  }
+  contract_h(P, d, m, a.ard, S, red, g22);
   __syncthreads();
   const double som = r2[2 + L];
   if (tid == 0) out[2] = 2.0 * r2[0] + g22[0] + sig2 * som;

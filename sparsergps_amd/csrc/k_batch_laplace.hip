@@ -27,13 +27,17 @@
 //                                                                    k_bl_gf, per problem
 // The first objective (before any update) is k_bl_obj without the update.  The likelihood enters
 // through LapLik<FAM>'s four row terms (sgp_lap_lik.h), as in the context route's kernels.
-// The segments, the 64-row steps, the per-row bounds test, k's operand layout (lane l on row
-// l & 15 and knots 4 s + (l >> 4)) and the rank updates through a wave-private transposition are
-// k_batch_fitc.hip's; S_Z and S_B have both operands scaled by the root of their positive weight,
-// S_a one operand scaled by a_i, which takes both signs.  f and Z are indexed by (problem, local
-// row), so aliased row ranges need nothing further.  A problem that stopped, failed or is
-// inactive returns at once from every launch.  Every sum and the maximum have a fixed order, no
-// kernel uses atomics, and nothing a problem computes reads another problem's data.
+// The segments, the 64-row steps and the per-row bounds test are the VI batch's (k_batch.hip);
+// k's operand layout (lane l on row l & 15 and knots 4 s + (l >> 4)), the rank updates through a
+// wave-private transposition, the tails of the row passes and the pieces of the m x m stages
+// are sgp_batch_dev.h's: S_Z and S_B have both operands scaled by the root of their positive
+// weight (rank_update_root), S_a one operand scaled by a_i, which takes both signs
+// (rank_update_signed).  This file keeps the row terms, G and the Newton iteration's vector
+// stages; k_bl_obj's body, k_bl_mmz's and k_bl_mm's build loops and k_bl_mm's posterior store
+// write a shared piece's text out where its function form cost time (each says so).  f and Z are indexed by (problem, local row), so aliased row ranges need nothing
+// further.  A problem that stopped, failed or is inactive returns at once from every launch.
+// Every sum and the maximum have a fixed order, no kernel uses atomics, and nothing a problem
+// computes reads another problem's data.
 #include <math.h>
 
 #include "sgp_internal.h"
@@ -42,119 +46,21 @@
 
 namespace {
 
-constexpr int FXS = 68;   // the wave-private k tile's row stride (doubles)
-
-// k of the step's rows in k_fit_scan's layout: e2[s] the scaled squared distance of row r16 of
-// the wave's 16 and knot 4 s + g, kf[s] the covariance (zero beyond the rows and the knots)
-#define SGP_BL_ROWS_K()                                                            \
-  const bool iv = step * 64 + wv * 16 + r16 < rows;                                \
-  const double* xr = xs + wv * 16 + r16;                                           \
-  double e2[SN], kf[SN];                                                           \
-  _Pragma("unroll") for (int s = 0; s < SN; ++s) e2[s] = 0.0;                      \
-  for (int c = 0; c < d; ++c) {                                                    \
-    const double xc = xr[c * 64], rl = rl_s[c];                                    \
-    const double* u = xu_s + (c * 4 + g) * SN;                                     \
-    _Pragma("unroll") for (int s = 0; s < SN; ++s) {                               \
-      const double t = (xc - u[s]) * rl;                                           \
-      e2[s] = fma(t, t, e2[s]);                                                    \
-    }                                                                              \
-  }                                                                                \
-  _Pragma("unroll") for (int s = 0; s < SN; ++s) {                                 \
-    const double v = sig2 * sgp_exp_nonpos(-0.5 * e2[s]);                          \
-    kf[s] = (iv && 4 * s + g < m) ? v : 0.0;                                       \
-  }
-
 // the step's X rows and its rows of f, y, mu, Z and the exposure (rv: 5 x 64)
-#define SGP_BL_STAGE()                                                             \
-  for (int q = tid; q < d * 64; q += 256) {                                        \
-    const int c = q >> 6, i = q & 63;                                              \
-    const int row = step * 64 + i;                                                 \
-    xs[q] = row < rows ? a.X[(int64_t)c * a.ldx + row0 + row] : 0.0;               \
-  }                                                                                \
-  if (tid < 64) {                                                                  \
-    const int row = step * 64 + tid;                                               \
-    const bool ok = row < rows;                                                    \
-    rv[tid] = ok ? l.f[loc + row] : 0.0;                                           \
-    rv[64 + tid] = ok ? a.y[row0 + row] : 0.0;                                     \
-    rv[128 + tid] = ok ? a.mu[row0 + row] : 0.0;                                   \
-    rv[192 + tid] = ok ? l.zv[loc + row] : 1.0;                                    \
-    rv[256 + tid] = (ok && l.expo) ? l.expo[row0 + row] : 1.0;                     \
-  }
-
-// sum over the lane's knots of acc o k, then over the four lane groups: every lane of a row
-// ends with the same bits
-template <int NT>
-__device__ __forceinline__ double row_dot(const d4* acc, const double* kf) {
-  double v = 0.0;
-#pragma unroll
-  for (int cb = 0; cb < NT; ++cb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v = fma(acc[cb][r], kf[4 * cb + r], v);
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-
-// k_i^T v for a vector staged as v_s[g * SN + s] = v[4 s + g]
-template <int SN>
-__device__ __forceinline__ double k_dot(const double* kf, const double* v_s, int g) {
-  double v = 0.0;
-#pragma unroll
-  for (int s = 0; s < SN; ++s) v = fma(kf[s], v_s[g * SN + s], v);
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-
-// the four waves' partial block pairs, added in wave order into lds (row stride 64), mirrored
-// into rec (row stride 64)
-template <int NT>
-__device__ __forceinline__ void store_pairs(const d4* acc, double* lds, double* __restrict__ rec) {
-  constexpr int Mp = 16 * NT;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, g = lane >> 4;
-  for (int w = 0; w < 4; ++w) {
-    __syncthreads();
-    if (wv == w) {
-      int p = 0;
-#pragma unroll
-      for (int bi = 0; bi < NT; ++bi)
-#pragma unroll
-        for (int bj = bi; bj < NT; ++bj, ++p)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            double* s = lds + (16 * bi + 4 * r + g) * MM + 16 * bj + r16;
-            *s = w ? *s + acc[p][r] : acc[p][r];
-          }
-    }
-  }
-  __syncthreads();
-  for (int q = tid; q < Mp * Mp; q += 256) {
-    const int i = q / Mp, j = q - i * Mp;
-    rec[i * MM + j] = (i >> 4) > (j >> 4) ? lds[j * MM + i] : lds[i * MM + j];
-  }
-}
-
-// the knots, the reciprocal length scales and (V of them) m-vectors into k's layout
-__device__ __forceinline__ void stage_knots(const double* __restrict__ P, int d, int Mp, int SN,
-                                            double* xu_s, double* rl_s) {
+__device__ __forceinline__ void stage_rows(const BatchArgs& a, const BatchLapArgs& l, int64_t row0,
+                                           int64_t loc, int rows, int step, double* xs,
+                                           double* rv) {
   const int tid = threadIdx.x;
-  for (int q = tid; q < d * Mp; q += 256) {
-    const int c = q / Mp, j = q - c * Mp;
-    xu_s[(c * 4 + (j & 3)) * SN + (j >> 2)] = P[BP_U + c * MM + j];
+  stage_x(a.X, a.ldx, row0, rows, step, a.d, xs);
+  if (tid < 64) {
+    const int row = step * 64 + tid;
+    const bool ok = row < rows;
+    rv[tid] = ok ? l.f[loc + row] : 0.0;
+    rv[64 + tid] = ok ? a.y[row0 + row] : 0.0;
+    rv[128 + tid] = ok ? a.mu[row0 + row] : 0.0;
+    rv[192 + tid] = ok ? l.zv[loc + row] : 1.0;
+    rv[256 + tid] = (ok && l.expo) ? l.expo[row0 + row] : 1.0;
   }
-  for (int q = tid; q < d; q += 256) rl_s[q] = P[BP_RL + q];
-}
-__device__ __forceinline__ void stage_vec(const double* __restrict__ src, int m, int Mp, int SN,
-                                          double* v_s) {
-  for (int q = threadIdx.x; q < Mp; q += 256) v_s[(q & 3) * SN + (q >> 2)] = q < m ? src[q] : 0.0;
-}
-
-// out_s[i] = sum_k M[i][k] v_s[k] for i < m (M in HBM, row stride 64); the caller synchronises
-__device__ __forceinline__ double mat_vec_row(const double* __restrict__ M, const double* v_s,
-                                              int i, int m) {
-  double s = 0.0;
-  for (int k = 0; k < m; ++k) s = fma(M[i * MM + k], v_s[k], s);
-  return s;
 }
 
 // x = Ainv b and, under the Bernoulli family, sec. 3.4's one refinement step
@@ -193,18 +99,12 @@ __global__ void __launch_bounds__(256) k_bl_k22(BatchArgs a, BatchLapArgs l) {
   const int prob = blockIdx.x, tid = threadIdx.x;
   const double* P = a.par + (int64_t)prob * a.pst;
   if (P[BP_ACTIVE] == 0.0) return;
-  const int d = a.d, m = (int)P[BP_M];
-  const double sig2 = P[BP_SIG2], dg = P[BP_TAU2] + P[BP_DELTA];   // quirk Q1
+  const int m = (int)P[BP_M];
   double* out = a.out + (int64_t)prob * BATCH_OUT;
   double* lw = l.lw + (int64_t)prob * BATCH_LW;
   double* lc = l.lc + (int64_t)prob * BATCH_LC;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    A[i * MM + j] = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j)) + (i == j ? dg : 0.0);
-  }
   double ld22 = 0.0;
-  const int st = sweep_spd(A, m, ck, &ld22);
+  const int st = k22_inverse(P, a.d, P[BP_TAU2] + P[BP_DELTA], A, ck, &ld22);   // quirk Q1
   if (tid == 0) {
     out[0] = st ? NAN : 0.0;
     out[1] = (double)st;
@@ -214,11 +114,7 @@ __global__ void __launch_bounds__(256) k_bl_k22(BatchArgs a, BatchLapArgs l) {
     lc[LC_OBJ] = 0.0;
   }
   if (st) return;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    lw[LW_A + i * MM + j] = A[i * MM + j];
-  }
+  for_mm(m, [&](int i, int j) { lw[LW_A + i * MM + j] = A[i * MM + j]; });
 }
 
 // ------------------------------------------------------------------------------ Z and S_Z
@@ -239,56 +135,29 @@ __device__ __forceinline__ void bl_passz_body(const BatchArgs& a, const BatchLap
   double* wt = wt_s + wv * 16 * FXS;
 
   stage_knots(P, d, Mp, SN, xu_s, rl_s);
-  for (int q = tid; q < Mp * Mp; q += 256) {
-    const int i = q / Mp, j = q - i * Mp;
-    pa_s[q] = (i < m && j < m) ? lw[LW_A + i * MM + j] : 0.0;
-  }
+  stage_mat(lw + LW_A, m, Mp, pa_s);
   d4 acc[NT * (NT + 1) / 2];
 #pragma unroll
   for (int p = 0; p < NT * (NT + 1) / 2; ++p) acc[p] = d4{0.0, 0.0, 0.0, 0.0};
 
   for (int step = 0; step * 64 < rows; ++step) {
     __syncthreads();
-    for (int q = tid; q < d * 64; q += 256) {
-      const int c = q >> 6, i = q & 63;
-      const int row = step * 64 + i;
-      xs[q] = row < rows ? a.X[(int64_t)c * a.ldx + row0 + row] : 0.0;
-    }
+    stage_x(a.X, a.ldx, row0, rows, step, d, xs);
     __syncthreads();
 
-    SGP_BL_ROWS_K()
+    double e2[SN], kf[SN];
+    const bool iv = rows_k<SN>(xs, xu_s, rl_s, d, m, sig2, rows, step, e2, kf);
     d4 qa[NT];
-#pragma unroll
-    for (int cb = 0; cb < NT; ++cb) qa[cb] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < SN; ++s)
-#pragma unroll
-      for (int cb = 0; cb < NT; ++cb)
-        qa[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa_s[(4 * s + g) * Mp + 16 * cb + r16],
-                                                      kf[s], qa[cb], 0, 0, 0);
+    kmat<NT>(pa_s, kf, qa);
     const double z = c0 - row_dot<NT>(qa, kf);   // newtrap_sparseGP.R:63-66
     if (g == 0) {
       const int i = wv * 16 + r16;
       if (iv) l.zv[loc + step * 64 + i] = z;
       sw_s[i] = iv ? sqrt(1.0 / z) : 0.0;
     }
-#pragma unroll
-    for (int s = 0; s < SN; ++s) wt[r16 * FXS + 4 * s + g] = kf[s];
+    put_ktile<SN>(wt, kf);
     __syncthreads();   // the k tile and the weights are read across the wave's lanes
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = 4 * q + g;
-      const double sq = sw_s[wv * 16 + i];
-      double kw[NT];
-#pragma unroll
-      for (int b = 0; b < NT; ++b) kw[b] = wt[i * FXS + 16 * b + r16] * sq;
-      int p = 0;
-#pragma unroll
-      for (int bi = 0; bi < NT; ++bi)
-#pragma unroll
-        for (int bj = bi; bj < NT; ++bj, ++p)
-          acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(kw[bi], kw[bj], acc[p], 0, 0, 0);
-    }
+    rank_update_root<NT, false>(wt, sw_s, nullptr, acc, nullptr);
   }
   store_pairs<NT>(acc, pa_s, rec);   // over A, which is dead
 }
@@ -304,12 +173,8 @@ __global__ void __launch_bounds__(256) k_bl_passz(BatchArgs a, BatchLapArgs l) {
   const int64_t row0 = a.seg_row0[seg], loc = l.seg_loc[seg];
   const int rows = a.seg_rows[seg];
   double* rec = a.rec1 + (int64_t)seg * BATCH_REC1;
-  switch (((int)P[BP_M] + 15) >> 4) {
-    case 1: bl_passz_body<1>(a, l, P, lw, row0, loc, rows, rec, xu_s, pa_s, vec_s, xs, wt_s); break;
-    case 2: bl_passz_body<2>(a, l, P, lw, row0, loc, rows, rec, xu_s, pa_s, vec_s, xs, wt_s); break;
-    case 3: bl_passz_body<3>(a, l, P, lw, row0, loc, rows, rec, xu_s, pa_s, vec_s, xs, wt_s); break;
-    default: bl_passz_body<4>(a, l, P, lw, row0, loc, rows, rec, xu_s, pa_s, vec_s, xs, wt_s); break;
-  }
+  SGP_BATCH_NT(P[BP_M],
+               bl_passz_body<NT>(a, l, P, lw, row0, loc, rows, rec, xu_s, pa_s, vec_s, xs, wt_s))
 }
 
 // ------------------------------------------------------------------------------ (K22 + S_Z)^-1
@@ -325,12 +190,12 @@ __global__ void __launch_bounds__(256) k_bl_mmz(BatchArgs a, BatchLapArgs l) {
   double* out = a.out + (int64_t)prob * BATCH_OUT;
   double* lw = l.lw + (int64_t)prob * BATCH_LW;
   const double* rec = a.rec1 + (int64_t)seg0 * BATCH_REC1;
+  // for_mm's map written out: as a lambda this loop cost two VGPRs and 5 % of the stage
   for (int e = tid; e < m * MM; e += 256) {
     const int i = e >> 6, j = e & (MM - 1);
     if (j >= m) continue;
     const double s = rec_sum(rec + i * MM + j, BATCH_REC1, nseg);
-    const double kuu = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j));
-    const double v = (kuu + (i == j ? dg : 0.0)) + s;
+    const double v = k22(P, d, i, j, sig2, dg) + s;
     Bm[i * MM + j] = v;
     lw[LW_BZ + i * MM + j] = v;
   }
@@ -344,11 +209,7 @@ __global__ void __launch_bounds__(256) k_bl_mmz(BatchArgs a, BatchLapArgs l) {
     }
     return;
   }
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    lw[LW_BZI + i * MM + j] = Bm[i * MM + j];
-  }
+  for_mm(m, [&](int i, int j) { lw[LW_BZI + i * MM + j] = Bm[i * MM + j]; });
 }
 
 // ------------------------------------------------------------------------------ NR, part a
@@ -381,10 +242,11 @@ __device__ __forceinline__ void bl_nra_body(const BatchArgs& a, const BatchLapAr
 
   for (int step = 0; step * 64 < rows; ++step) {
     __syncthreads();
-    SGP_BL_STAGE()
+    stage_rows(a, l, row0, loc, rows, step, xs, rv);
     __syncthreads();
 
-    SGP_BL_ROWS_K()
+    double e2[SN], kf[SN];
+    const bool iv = rows_k<SN>(xs, xu_s, rl_s, d, m, sig2, rows, step, e2, kf);
     const double y1 = k_dot<SN>(kf, x1_s, g);
     if (g == 0) {
       const int i = wv * 16 + r16;
@@ -398,8 +260,7 @@ __device__ __forceinline__ void bl_nra_body(const BatchArgs& a, const BatchLapAr
       if (iv) gmax = fmax(gmax, fabs(gp));
       wr_s[i] = iv ? (1.0 / om) * gp : 0.0;
     }
-#pragma unroll
-    for (int s = 0; s < SN; ++s) wt[r16 * FXS + 4 * s + g] = kf[s];
+    put_ktile<SN>(wt, kf);
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -410,16 +271,10 @@ __device__ __forceinline__ void bl_nra_body(const BatchArgs& a, const BatchLapAr
     }
   }
   __syncthreads();
-#pragma unroll
-  for (int b = 0; b < NT; ++b) {
-    double t = tacc[b];
-    t += __shfl_xor(t, 16, 64);
-    t += __shfl_xor(t, 32, 64);
-    if (g == 0) tw[wv * MM + 16 * b + r16] = t;
-  }
+  fold_tacc<NT>(tacc, tw);
   if (g == 0) red[wv * 16 + r16] = gmax;
   __syncthreads();
-  if (tid < Mp) rec[tid] = ((tw[tid] + tw[MM + tid]) + tw[2 * MM + tid]) + tw[3 * MM + tid];
+  if (tid < Mp) rec[tid] = wave_sum4(tw, tid);
   if (tid == 0) {
     double v = 0.0;
     for (int q = 0; q < 64; ++q) v = fmax(v, red[q]);   // wave, then row lane
@@ -439,15 +294,8 @@ __global__ void __launch_bounds__(256) k_bl_nra(BatchArgs a, BatchLapArgs l) {
   const int64_t row0 = a.seg_row0[seg], loc = l.seg_loc[seg];
   const int rows = a.seg_rows[seg];
   double* rec = l.lrec + (int64_t)seg * BATCH_LREC;
-#define SGP_BL_CASE(NT) \
-  bl_nra_body<NT, FAM>(a, l, P, lw, row0, loc, rows, rec, xu_s, vec_s, xs, wt_s, tw); break;
-  switch (((int)P[BP_M] + 15) >> 4) {
-    case 1: SGP_BL_CASE(1)
-    case 2: SGP_BL_CASE(2)
-    case 3: SGP_BL_CASE(3)
-    default: SGP_BL_CASE(4)
-  }
-#undef SGP_BL_CASE
+  SGP_BATCH_NT(P[BP_M], bl_nra_body<NT, FAM>(a, l, P, lw, row0, loc, rows, rec, xu_s, vec_s, xs,
+                                             wt_s, tw))
 }
 
 // ------------------------------------------------------------------------------ x2 = C v2
@@ -507,10 +355,32 @@ __device__ __forceinline__ void bl_obj_body(const BatchArgs& a, const BatchLapAr
 
   for (int step = 0; step * 64 < rows; ++step) {
     __syncthreads();
-    SGP_BL_STAGE()
+    stage_rows(a, l, row0, loc, rows, step, xs, rv);
     __syncthreads();
 
-    SGP_BL_ROWS_K()
+    // rows_k, rank_update_root<NT, true> and pass1_tail written out in this body: through the
+    // header's functions this kernel, the largest of the file, came out 1 % slower; written out
+    // it compiles to the registers and spills it had before they were shared.  The text is
+    // theirs, operation for operation.
+    const bool iv = step * 64 + wv * 16 + r16 < rows;
+    const double* xr = xs + wv * 16 + r16;
+    double e2[SN], kf[SN];
+#pragma unroll
+    for (int s = 0; s < SN; ++s) e2[s] = 0.0;
+    for (int c = 0; c < d; ++c) {
+      const double xc = xr[c * 64], rl = rl_s[c];
+      const double* u = xu_s + (c * 4 + g) * SN;
+#pragma unroll
+      for (int s = 0; s < SN; ++s) {
+        const double t = (xc - u[s]) * rl;
+        e2[s] = fma(t, t, e2[s]);
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < SN; ++s) {
+      const double v = sig2 * sgp_exp_nonpos(-0.5 * e2[s]);
+      kf[s] = (iv && 4 * s + g < m) ? v : 0.0;
+    }
     double y1 = 0.0, y2 = 0.0;
     if (upd) {
       y1 = k_dot<SN>(kf, x1_s, g);
@@ -544,8 +414,7 @@ __device__ __forceinline__ void bl_obj_body(const BatchArgs& a, const BatchLapAr
       sw_s[i] = iv ? sqrt(bi) : 0.0;
       wr_s[i] = iv ? tv : 0.0;
     }
-#pragma unroll
-    for (int s = 0; s < SN; ++s) wt[r16 * FXS + 4 * s + g] = kf[s];
+    put_ktile<SN>(wt, kf);
     __syncthreads();   // the k tile and the weights are read across the wave's lanes
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -601,17 +470,8 @@ __global__ void __launch_bounds__(256) k_bl_obj(BatchArgs a, BatchLapArgs l, int
   const int64_t row0 = a.seg_row0[seg], loc = l.seg_loc[seg];
   const int rows = a.seg_rows[seg];
   double* rec = a.rec1 + (int64_t)seg * BATCH_REC1;
-#define SGP_BL_CASE(NT)                                                                        \
-  bl_obj_body<NT, FAM>(a, l, P, lw, upd != 0, row0, loc, rows, rec, xu_s, S_s, vec_s, xs, wt_s, \
-                       tw);                                                                    \
-  break;
-  switch (((int)P[BP_M] + 15) >> 4) {
-    case 1: SGP_BL_CASE(1)
-    case 2: SGP_BL_CASE(2)
-    case 3: SGP_BL_CASE(3)
-    default: SGP_BL_CASE(4)
-  }
-#undef SGP_BL_CASE
+  SGP_BATCH_NT(P[BP_M], bl_obj_body<NT, FAM>(a, l, P, lw, upd != 0, row0, loc, rows, rec, xu_s,
+                                             S_s, vec_s, xs, wt_s, tw))
 }
 
 // ------------------------------------------------------------------------------ C, x1, the objective, the stop rule
@@ -635,12 +495,12 @@ __global__ void __launch_bounds__(256) k_bl_mm(BatchArgs a, BatchLapArgs l, int 
   const double rr = rec_sum(rec + BR_RR, BATCH_REC1, nseg);
   const double logpy = rec_sum(rec + BR_RR + 1, BATCH_REC1, nseg);
   const double logz2 = rec_sum(rec + BR_RR + 2, BATCH_REC1, nseg);
+  // for_mm's map written out, as in k_bl_mmz: the stage runs once per Newton iteration
   for (int e = tid; e < m * MM; e += 256) {
     const int i = e >> 6, j = e & (MM - 1);
     if (j >= m) continue;
     const double s = rec_sum(rec + i * MM + j, BATCH_REC1, nseg);
-    const double kuu = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j));
-    const double v = (kuu + (i == j ? dg : 0.0)) + s;
+    const double v = k22(P, d, i, j, sig2, dg) + s;
     Bm[i * MM + j] = v;
     lw[LW_BB + i * MM + j] = v;
   }
@@ -665,11 +525,7 @@ __global__ void __launch_bounds__(256) k_bl_mm(BatchArgs a, BatchLapArgs l, int 
     return;
   }
   double* Cm = lw + LW_C + (it & 1) * BR_T;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    Cm[i * MM + j] = Bm[i * MM + j];
-  }
+  for_mm(m, [&](int i, int j) { Cm[i * MM + j] = Bm[i * MM + j]; });
   solve_refined<FAM>(lw + LW_BZ, lw + LW_BZI, t_s, x_s, r_s, m);
   const double tu = block_sum(tid < m ? t_s[tid] * x_s[tid] : 0.0, red);
   // laplace_approx_obj_funs.R:158-172: quad + log p(y|f) + det_part_1 + det_part_2
@@ -690,7 +546,9 @@ __global__ void __launch_bounds__(256) k_bl_mm(BatchArgs a, BatchLapArgs l, int 
   }
   if (run) return;
   // the knot posterior's state (newtrap_sparseGP.R:137-176), where VI and FITC leave theirs:
-  // (K22 + S_B(W_prev))^-1 with the loop's last, one-step-stale W, and x1 at the mode
+  // (K22 + S_B(W_prev))^-1 with the loop's last, one-step-stale W, and x1 at the mode.  Not
+  // store_post: the matrix comes from HBM or from LDS by entry, and two inlined copies of the
+  // helper moved this kernel's schedule (the stage is the largest of a cold Bernoulli run)
   double* post = a.post + (int64_t)prob * a.post_stride;
   const double* Cp = lw + LW_C + ((it + 1) & 1) * BR_T;   // the previous objective's C
   for (int e = tid; e < m * MM; e += 256) {
@@ -734,10 +592,7 @@ __device__ __forceinline__ void bl_ga_body(const BatchArgs& a, const BatchLapArg
 
   stage_knots(P, d, Mp, SN, xu_s, rl_s);
   stage_vec(lw + LW_X1, m, Mp, SN, x1_s);
-  for (int q = tid; q < Mp * Mp; q += 256) {
-    const int i = q / Mp, j = q - i * Mp;
-    pb_s[q] = (i < m && j < m) ? Cm[i * MM + j] : 0.0;
-  }
+  stage_mat(Cm, m, Mp, pb_s);
   double tacc[3][NT];
 #pragma unroll
   for (int v = 0; v < 3; ++v)
@@ -746,19 +601,13 @@ __device__ __forceinline__ void bl_ga_body(const BatchArgs& a, const BatchLapArg
 
   for (int step = 0; step * 64 < rows; ++step) {
     __syncthreads();
-    SGP_BL_STAGE()
+    stage_rows(a, l, row0, loc, rows, step, xs, rv);
     __syncthreads();
 
-    SGP_BL_ROWS_K()
+    double e2[SN], kf[SN];
+    const bool iv = rows_k<SN>(xs, xu_s, rl_s, d, m, sig2, rows, step, e2, kf);
     d4 qb[NT];
-#pragma unroll
-    for (int cb = 0; cb < NT; ++cb) qb[cb] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < SN; ++s)
-#pragma unroll
-      for (int cb = 0; cb < NT; ++cb)
-        qb[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(pb_s[(4 * s + g) * Mp + 16 * cb + r16],
-                                                      kf[s], qb[cb], 0, 0, 0);
+    kmat<NT>(pb_s, kf, qb);
     const double pi = row_dot<NT>(qb, kf);
     const double y1 = k_dot<SN>(kf, x1_s, g);
     if (g == 0) {
@@ -776,8 +625,7 @@ __device__ __forceinline__ void bl_ga_body(const BatchArgs& a, const BatchLapArg
       w3_s[MM + i] = iv ? lik.d1(yi) : 0.0;
       w3_s[2 * MM + i] = iv ? bi * sv : 0.0;
     }
-#pragma unroll
-    for (int s = 0; s < SN; ++s) wt[r16 * FXS + 4 * s + g] = kf[s];
+    put_ktile<SN>(wt, kf);
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -795,21 +643,11 @@ __device__ __forceinline__ void bl_ga_body(const BatchArgs& a, const BatchLapArg
   }
   __syncthreads();
 #pragma unroll
-  for (int v = 0; v < 3; ++v)
-#pragma unroll
-    for (int b = 0; b < NT; ++b) {
-      double t = tacc[v][b];
-      t += __shfl_xor(t, 16, 64);
-      t += __shfl_xor(t, 32, 64);
-      if (g == 0) tw[(v * 4 + wv) * MM + 16 * b + r16] = t;
-    }
+  for (int v = 0; v < 3; ++v) fold_tacc<NT>(tacc[v], tw + v * 4 * MM);
   __syncthreads();
   for (int q = tid; q < 3 * MM; q += 256) {
     const int v = q >> 6, j = q & 63;
-    if (j < Mp) {
-      const double* t = tw + v * 4 * MM + j;
-      rec[v * MM + j] = ((t[0] + t[MM]) + t[2 * MM]) + t[3 * MM];
-    }
+    if (j < Mp) rec[v * MM + j] = wave_sum4(tw + v * 4 * MM, j);
   }
 }
 
@@ -828,15 +666,8 @@ __global__ void __launch_bounds__(256) k_bl_ga(BatchArgs a, BatchLapArgs l) {
   const int64_t row0 = a.seg_row0[seg], loc = l.seg_loc[seg];
   const int rows = a.seg_rows[seg];
   double* rec = l.lrec + (int64_t)seg * BATCH_LREC;
-#define SGP_BL_CASE(NT) \
-  bl_ga_body<NT, FAM>(a, l, P, lw, Cm, row0, loc, rows, rec, xu_s, pb_s, vec_s, xs, wt_s, tw); break;
-  switch (((int)P[BP_M] + 15) >> 4) {
-    case 1: SGP_BL_CASE(1)
-    case 2: SGP_BL_CASE(2)
-    case 3: SGP_BL_CASE(3)
-    default: SGP_BL_CASE(4)
-  }
-#undef SGP_BL_CASE
+  SGP_BATCH_NT(P[BP_M], bl_ga_body<NT, FAM>(a, l, P, lw, Cm, row0, loc, rows, rec, xu_s, pb_s,
+                                            vec_s, xs, wt_s, tw))
 }
 
 // ------------------------------------------------------------------------------ s, GG, C w
@@ -864,7 +695,6 @@ __global__ void __launch_bounds__(256) k_bl_gm(BatchArgs a, BatchLapArgs l) {
 }
 
 // ------------------------------------------------------------------------------ gradient, part b
-// el_s (ARD): [c][wave][16] slots, one per row lane of a wave, as in k_bf_pass2
 template <int NT, bool ARD, int FAM>
 __device__ __forceinline__ void bl_gb_body(const BatchArgs& a, const BatchLapArgs& l,
                                            const double* __restrict__ P,
@@ -892,12 +722,8 @@ __device__ __forceinline__ void bl_gb_body(const BatchArgs& a, const BatchLapArg
   stage_vec(lw + LW_CW, m, Mp, SN, cw_s);
   stage_vec(lw + LW_S, m, Mp, SN, s_s);
   stage_vec(lw + LW_GG, m, Mp, SN, gg_s);
-  for (int q = tid; q < Mp * Mp; q += 256) {
-    const int i = q / Mp, j = q - i * Mp;
-    const bool in = i < m && j < m;
-    pa_s[q] = in ? lw[LW_A + i * MM + j] : 0.0;
-    pb_s[q] = in ? Cm[i * MM + j] : 0.0;
-  }
+  stage_mat(lw + LW_A, m, Mp, pa_s);
+  stage_mat(Cm, m, Mp, pb_s);
   if (ARD)
     for (int q = tid; q < d * 64; q += 256) el_s[q] = 0.0;
 
@@ -908,22 +734,13 @@ __device__ __forceinline__ void bl_gb_body(const BatchArgs& a, const BatchLapArg
 
   for (int step = 0; step * 64 < rows; ++step) {
     __syncthreads();
-    SGP_BL_STAGE()
+    stage_rows(a, l, row0, loc, rows, step, xs, rv);
     __syncthreads();
 
-    SGP_BL_ROWS_K()
+    double e2[SN], kf[SN];
+    const bool iv = rows_k<SN>(xs, xu_s, rl_s, d, m, sig2, rows, step, e2, kf);
     d4 qa[NT], qb[NT];
-#pragma unroll
-    for (int cb = 0; cb < NT; ++cb) qa[cb] = qb[cb] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < SN; ++s)
-#pragma unroll
-      for (int cb = 0; cb < NT; ++cb) {
-        qa[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa_s[(4 * s + g) * Mp + 16 * cb + r16],
-                                                      kf[s], qa[cb], 0, 0, 0);
-        qb[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(pb_s[(4 * s + g) * Mp + 16 * cb + r16],
-                                                      kf[s], qb[cb], 0, 0, 0);
-      }
+    kmat2<NT>(pa_s, pb_s, kf, qa, qb);
     const double pi = row_dot<NT>(qb, kf);
     const double y1 = k_dot<SN>(kf, x1_s, g);
     const double y3 = k_dot<SN>(kf, cw_s, g);
@@ -951,80 +768,20 @@ __device__ __forceinline__ void bl_gb_body(const BatchArgs& a, const BatchLapArg
         om_s[i] = ai;
       }
     }
-    double w[SN];
-#pragma unroll
-    for (int cb = 0; cb < NT; ++cb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int s = 4 * cb + r;
-        // G = c2 s^T - h GG^T - B K C - 2 a K A
-        const double gv = fma(c2, s_s[g * SN + s], -fma(hi, gg_s[g * SN + s],
-                                                        fma(bi, qb[cb][r], 2.0 * ai * qa[cb][r])));
-        w[s] = gv * kf[s];
-        esig += w[s];
-        if (!ARD) el = fma(w[s], e2[s], el);
-        // quirk Q5: the tau derivative of a pair whose raw differences are all zero
-        if (e2[s] == 0.0 && iv && 4 * s + g < m) csum += gv;
-      }
-    if (ARD)
-      for (int c = 0; c < d; ++c) {
-        const double xc = xr[c * 64], rl = rl_s[c];
-        const double* u = xu_s + (c * 4 + g) * SN;
-        double v = 0.0;
-#pragma unroll
-        for (int s = 0; s < SN; ++s) {
-          const double t = (xc - u[s]) * rl;
-          v = fma(w[s], t * t, v);
-        }
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
-        if (g == 0) el_s[(c * 4 + wv) * 16 + r16] += v;   // the lane's own slot
-      }
-#pragma unroll
-    for (int s = 0; s < SN; ++s) wt[r16 * FXS + 4 * s + g] = kf[s];
+    // G = c2 s^T - h GG^T - B K C - 2 a K A
+    grad_terms<NT, ARD>(
+        [&](int cb, int r, int s) {
+          return fma(c2, s_s[g * SN + s],
+                     -fma(hi, gg_s[g * SN + s], fma(bi, qb[cb][r], 2.0 * ai * qa[cb][r])));
+        },
+        kf, e2, iv, m, d, xs, xu_s, rl_s, el_s, esig, el, csum);
+    put_ktile<SN>(wt, kf);
     __syncthreads();   // the k tile and a are read across the wave's lanes
-    // S_a[16 bi + i][16 bj + j] += sum over the wave's 16 rows: A[i][row] = a k, B[row][j] = k:
-    // a takes both signs, so only one operand carries it
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = 4 * q + g;
-      const double oi = om_s[wv * 16 + i];
-      double k1[NT], ko[NT];
-#pragma unroll
-      for (int b = 0; b < NT; ++b) {
-        k1[b] = wt[i * FXS + 16 * b + r16];
-        ko[b] = k1[b] * oi;
-      }
-      int p = 0;
-#pragma unroll
-      for (int bi2 = 0; bi2 < NT; ++bi2)
-#pragma unroll
-        for (int bj = bi2; bj < NT; ++bj, ++p)
-          acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(ko[bi2], k1[bj], acc[p], 0, 0, 0);
-    }
+    rank_update_signed<NT>(wt, om_s, acc);   // S_a
   }
 
   store_pairs<NT>(acc, pa_s, rec);   // over A, which is dead
-  const double e0 = block_sum(esig, red);
-  const double e1 = block_sum(csum, red);
-  const double e2s = block_sum(som, red);
-  const int L = ARD ? d : 1;
-  if (ARD) {
-    __syncthreads();
-    if (tid < d) {
-      double v = 0.0;
-      for (int q = 0; q < 64; ++q) v += el_s[tid * 64 + q];   // wave, then row lane
-      rec[BQ_W + 1 + tid] = v;
-    }
-  } else {
-    const double e3 = block_sum(el, red);
-    if (tid == 0) rec[BQ_W + 1] = e3;
-  }
-  if (tid == 0) {
-    rec[BQ_W] = e0;
-    rec[BQ_W + 1 + L] = e1;
-    rec[BQ_W + 2 + L] = e2s;
-  }
+  grad_tail<ARD>(esig, el, csum, som, d, red, el_s, rec);
 }
 
 template <bool ARD, int FAM>
@@ -1042,24 +799,15 @@ __global__ void __launch_bounds__(256) k_bl_gb(BatchArgs a, BatchLapArgs l) {
   const int64_t row0 = a.seg_row0[seg], loc = l.seg_loc[seg];
   const int rows = a.seg_rows[seg];
   double* rec = a.rec4 + (int64_t)seg * BATCH_REC4;
-#define SGP_BL_CASE(NT)                                                                         \
-  bl_gb_body<NT, ARD, FAM>(a, l, P, lw, Cm, row0, loc, rows, rec, xu_s, pa_s, pb_s, vec_s, xs, \
-                           wt_s, red, el_s);                                                    \
-  break;
-  switch (((int)P[BP_M] + 15) >> 4) {
-    case 1: SGP_BL_CASE(1)
-    case 2: SGP_BL_CASE(2)
-    case 3: SGP_BL_CASE(3)
-    default: SGP_BL_CASE(4)
-  }
-#undef SGP_BL_CASE
+  SGP_BATCH_NT(P[BP_M], bl_gb_body<NT, ARD, FAM>(a, l, P, lw, Cm, row0, loc, rows, rec, xu_s, pa_s,
+                                                 pb_s, vec_s, xs, wt_s, red, el_s))
 }
 
 // ------------------------------------------------------------------------------ G22 and finish
 // G22 = (K22^-1 - C) / 2 - s s^T / 2 + (C w GG^T + GG (C w)^T) / 4 + K22^-1 S_a K22^-1, contracted
-// with dK22 / dlog theta (sigma: 2 Kuu; l: Kuu |D|^2 / l^2; l_c: Kuu (D_c / l_c)^2; tau: 2 tau^2
-// where two knots coincide, the diagonal included: quirk Q5), then dlogq_dcov_par's gradient
-// from the segments' sums (A1 = 2 sigma^2 for sigma, 2 tau^2 for tau)
+// with dK22 / dlog theta (contract_h; tau: 2 tau^2 where two knots coincide, the diagonal
+// included: quirk Q5), then dlogq_dcov_par's gradient from the segments' sums (A1 = 2 sigma^2
+// for sigma, 2 tau^2 for tau)
 __global__ void __launch_bounds__(256) k_bl_gf(BatchArgs a, BatchLapArgs l) {
   __shared__ __attribute__((aligned(16))) double A[MM * MM], Ci[MM * MM], S[MM * MM], T[MM * MM];
   __shared__ double s_s[MM], gg_s[MM], cw_s[MM], red[256], r2[SGP_MAXD + 4], g22[SGP_MAXD + 2];
@@ -1075,13 +823,11 @@ __global__ void __launch_bounds__(256) k_bl_gf(BatchArgs a, BatchLapArgs l) {
   const double sig2 = P[BP_SIG2], tau2 = P[BP_TAU2];
   const int seg0 = (int)P[BP_SEG0], nseg = (int)P[BP_NSEG];
   const double* rec = a.rec4 + (int64_t)seg0 * BATCH_REC4;
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
+  for_mm(m, [&](int i, int j) {
     A[i * MM + j] = lw[LW_A + i * MM + j];
     Ci[i * MM + j] = Cm[i * MM + j];
     S[i * MM + j] = rec_sum(rec + i * MM + j, BATCH_REC4, nseg);
-  }
+  });
   if (tid < m) {
     s_s[tid] = lw[LW_S + tid];
     gg_s[tid] = lw[LW_GG + tid];
@@ -1089,60 +835,21 @@ __global__ void __launch_bounds__(256) k_bl_gf(BatchArgs a, BatchLapArgs l) {
   }
   if (tid < L + 3) r2[tid] = rec_sum(rec + BQ_W + tid, BATCH_REC4, nseg);
   __syncthreads();
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    double s = 0.0;
-    for (int k = 0; k < m; ++k) s = fma(A[i * MM + k], S[k * MM + j], s);
-    T[i * MM + j] = s;
-  }
-  __syncthreads();
+  sandwich(A, S, T, m);
   double cg = 0.0;   // G22 over the coincident knot pairs
-  for (int e = tid; e < m * MM; e += 256) {
-    const int i = e >> 6, j = e & (MM - 1);
-    if (j >= m) continue;
-    double s = 0.0;
-    for (int k = 0; k < m; ++k) s = fma(T[i * MM + k], A[k * MM + j], s);
+  for_mm(m, [&](int i, int j) {
+    const double s = dot_mm(T, A, i, j, m);
     const double gv = 0.5 * (A[i * MM + j] - Ci[i * MM + j]) - 0.5 * s_s[i] * s_s[j] +
                       0.25 * (cw_s[i] * gg_s[j] + gg_s[i] * cw_s[j]) + s;
-    const double kuu = sig2 * sgp_exp_nonpos(-0.5 * knot_dist2(P, d, i, j));
     bool same = true;
     for (int c = 0; c < d; ++c) same = same && P[BP_U + c * MM + i] == P[BP_U + c * MM + j];
     if (same) cg += gv;
-    S[i * MM + j] = gv * kuu;   // H: S is dead once T stands
-  }
+    S[i * MM + j] = gv * kuu(P, d, i, j, sig2);   // H: S is dead once T stands
+  });
   __syncthreads();
   const double cgs = block_sum(cg, red);
-  double h = 0.0;
-  for (int e = tid; e < m * MM; e += 256)
-    if ((e & (MM - 1)) < m) h += S[e];
-  const double hs = block_sum(h, red);
-  if (tid == 0) {
-    g22[0] = 2.0 * hs;
-    g22[SGP_MAXD + 1] = cgs;
-  }
-  if (a.ard) {
-    for (int c = 0; c < d; ++c) {
-      double v = 0.0;
-      for (int e = tid; e < m * MM; e += 256) {
-        const int i = e >> 6, j = e & (MM - 1);
-        if (j >= m) continue;
-        const double t = (P[BP_U + c * MM + i] - P[BP_U + c * MM + j]) * P[BP_RL + c];
-        v = fma(S[i * MM + j], t * t, v);
-      }
-      const double vs = block_sum(v, red);
-      if (tid == 0) g22[1 + c] = vs;
-    }
-  } else {
-    double v = 0.0;
-    for (int e = tid; e < m * MM; e += 256) {
-      const int i = e >> 6, j = e & (MM - 1);
-      if (j >= m) continue;
-      v = fma(S[i * MM + j], knot_dist2(P, d, i, j), v);
-    }
-    const double vs = block_sum(v, red);
-    if (tid == 0) g22[1] = vs;
-  }
+  if (tid == 0) g22[SGP_MAXD + 1] = cgs;
+  contract_h(P, d, m, a.ard, S, red, g22);
   __syncthreads();
   const double suma = r2[2 + L];
   if (tid == 0) out[2] = 2.0 * r2[0] + g22[0] + 2.0 * sig2 * suma;
